@@ -16,7 +16,11 @@ checked: counts and value by closed forms, the remoteness against the
 CPU restatement's solve of the same workload (tests/golden/checksums.json,
 or this run's cpu_baseline).
 
-Prints ONE JSON line (rank 0).  Fields beyond the driver contract:
+A plain run sets up, warms up, times the --steps solves, checks them, writes
+--dump-outputs if asked and prints ONE JSON line (rank 0): the headline
+figure, ms_per_step and what describes the run.  --dump-outputs DIR writes
+what the last timed solve left (dump_outputs below).  Everything that takes
+runs of its own comes with --full only, as further fields of the line:
   roofline      dominant kernel, HIP-event-timed average launch duration;
                 achieved/frac on the bytes the layout must move (compulsory:
                 own words written, live words of the two child rows read once,
@@ -412,6 +416,48 @@ def keyed_record(device):
     return out
 
 
+DUMP_SAMPLE = 1 << 20  # table positions read back by --dump-outputs (20 MB on disk)
+DUMP_SEED = 20240531
+
+
+def dump_outputs(out_dir, solver, result, positions):
+    """What a caller of the timed path holds after the last timed solve, as
+    DIR/<name>.npy:
+      result            float64[8]: the SolveResult's root value, root
+                        remoteness, positions, edges, primitives, levels,
+                        widest level, word bits
+      sample_keys       float64[n]: a fixed, seeded sample of the table's keys
+                        (key 0, the root, n - 2 drawn uniformly; a sum game's
+                        keys are the ranks 0..positions-1, all reachable)
+      sample_value      float32[n]: Solver.query's value code of each
+      sample_remoteness float32[n]: its remoteness
+      table_fingerprint float64[9]: Solver.checksum of the whole table -- the
+                        64-bit fingerprint in four 16-bit pieces, high first,
+                        then the position count and the W/L/T/D histogram
+    Shards of an N-GPU run answer for the keys they own only: there rank 0
+    writes `result` alone."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    r = result
+    np.save(os.path.join(out_dir, "result.npy"),
+            np.array([r.root_value, r.root_remoteness, r.positions, r.edges, r.primitives, r.levels,
+                      r.max_level_width, r.extra.get("word_bits") or 0], np.float64))
+    if solver.world > 1:
+        return
+    rng = np.random.default_rng(DUMP_SEED)
+    keys = np.concatenate([np.array([0, positions - 1], np.uint64),
+                           rng.integers(0, positions, size=DUMP_SAMPLE - 2, dtype=np.uint64)])
+    w = solver.query(keys)
+    np.save(os.path.join(out_dir, "sample_keys.npy"), keys.astype(np.float64))
+    np.save(os.path.join(out_dir, "sample_value.npy"), (w & 3).astype(np.float32))
+    np.save(os.path.join(out_dir, "sample_remoteness.npy"), (w >> 2).astype(np.float32))
+    ck = solver.checksum()
+    c = int(ck["checksum"], 16)
+    np.save(os.path.join(out_dir, "table_fingerprint.npy"),
+            np.array([(c >> s) & 0xFFFF for s in (48, 32, 16, 0)]
+                     + [ck[k] for k in ("positions", "win", "loss", "tie", "draw")], np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -419,9 +465,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--heaps", default=None,
                     help="override the synthetic heaps, e.g. 31:31:31:31")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the roofline's kernel-timing solve, "
+                         "the toot 6x4 keyed sub-record, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--no-keyed", action="store_true",
-                    help="skip the toot 6x4 keyed-table sub-record")
+                    help="with --full: skip the toot 6x4 keyed-table sub-record")
     ap.add_argument("--layout", default="auto", choices=["auto", "planes", "dense", "hashed"])
     ap.add_argument("--transport", default="rccl", choices=["rccl", "host"],
                     help="N>1 halo exchange: RCCL (one GPU per rank), or host-staged over "
@@ -501,14 +553,84 @@ def main():
         if (x.positions, x.edges) != (P, E) or x.root_line.split()[0] != root_value:
             raise SystemExit("WRONG RESULT: %d positions, %d edges, %s; expected %d, %d, %s"
                              % (x.positions, x.edges, x.root_line, P, E, root_value))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, solver, r, P)
 
-    # roofline of the dominant kernel: one extra solve with HIP events
-    # around every launch, on the stream the kernels run on
+    word_bits = r.extra.get("word_bits", 32) or 32
+    workload = "sum_four_to_one heaps=%s" % ":".join(map(str, heaps))
+    roof, tr = roofline(solver, layout, heaps, world, workload, word_bits) if args.full else (None, None)
+
+    # root remoteness: the CPU restatement's solve of the same workload
+    root_ref, root_src = None, None
+    g = golden_for_params("sum_four_to_one", params)
+    if g is not None:
+        root_ref, root_src = g["root_line"], "tests/golden/checksums.json (oracle_mt)"
+    cpu = None
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        cpu, cpu_root = cpu_baseline(params)
+        if root_ref is None:
+            root_ref, root_src = cpu_root, "cpu_baseline (oracle_mt) of this run"
+        elif cpu_root != root_ref:
+            raise SystemExit("CPU restatement disagrees with its golden: %s vs %s" % (cpu_root, root_ref))
+    if root_ref is not None:
+        for x in results + ([tr] if tr is not None else []):
+            if x.root_line != root_ref:
+                raise SystemExit("WRONG ROOT: %s, the CPU restatement gives %s" % (x.root_line, root_ref))
+
+    line = {
+        "metric": "positions solved/sec (node)",
+        "value": P * args.steps / elapsed,
+        "unit": "positions/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": ("u%d order-form words, integer (%s table: keys implicit in the slot)" % (word_bits, layout)
+                  if layout in ("dense", "planes") else "u64 keys / u32 words, integer"),
+        "data": "synthetic: sum of Four-To-One heaps, fully determined state space",
+        "config": {"workload": workload,
+                   "positions_per_gpu": P // world, "edges_per_gpu": E // world,
+                   "levels": r.levels, "root": r.root_line, "root_checked_against": root_src,
+                   "layout": layout,
+                   "parallelism": ((("row deal: heap 1 in 32-row slabs x%d, each level's last two rows per plane "
+                                     "streamed to the next rank" if layout == "planes" and heaps[1] != 31 else
+                                     "staged pipeline: one block of the top heap per rank x%d, halo rows "
+                                     "streamed to the next rank" if layout == "planes" else
+                                     "round-robin top-heap blocks x%d, one halo exchange per level") % world
+                                    + ", %s" % ("host-staged (gloo, all ranks on one GPU: rehearsal, not a "
+                                                "performance figure)" if host else "RCCL"))
+                                   if world > 1 else "1 GPU")},
+        "step_issue": ("queued solves (gm_solver_solve_async, <= %d outstanding): back to back on the GPU, "
+                       "each collected and checked; solve_wall = one solve's device span" % QDEPTH
+                       if queued else "one blocking solve() per step"),
+        "phase_ms": {"forward": r.ms_forward, "backward": r.ms_backward,
+                     "solve_wall": r.ms_total},
+    }
+    if args.full:
+        line["roofline"] = roof
+        line["phase_ms"].update(expand_kernels=tr.ms_expand_kernels, resolve_kernels=tr.ms_resolve_kernels)
+    if args.full and rank == 0 and world == 1 and not args.no_keyed:
+        del solver
+        torch.cuda.empty_cache()
+        line["keyed"] = keyed_record("cuda:%d" % local)
+    if cpu is not None:
+        line["cpu_baseline"] = cpu
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def roofline(solver, layout, heaps, world, workload, word_bits):
+    """--full: the roofline record of the dominant kernel, from one extra
+    solve with HIP events around every launch, on the stream the kernels run
+    on; that solve's result comes back with it."""
     solver.set_kernel_timing(True)
     tr = solver.solve()
     solver.set_kernel_timing(False)
-    word_bits = tr.extra.get("word_bits", 32) or 32
-    workload = "sum_four_to_one heaps=%s" % ":".join(map(str, heaps))
     if layout == "planes":
         m = plane_bytes(heaps, word_bits // 8)
         # plane_bytes counts 32 x 32 planes over the outer heaps: per rank
@@ -575,69 +697,7 @@ def main():
                           else "an event pair around each launch, summed")),
             "launches": kn, "ms_kernel_total": kms, "ms_per_launch": kms / kn,
             "algorithmic_bytes_total": kb}
-
-    # root remoteness: the CPU restatement's solve of the same workload
-    root_ref, root_src = None, None
-    g = golden_for_params("sum_four_to_one", params)
-    if g is not None:
-        root_ref, root_src = g["root_line"], "tests/golden/checksums.json (oracle_mt)"
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu, cpu_root = cpu_baseline(params)
-        if root_ref is None:
-            root_ref, root_src = cpu_root, "cpu_baseline (oracle_mt) of this run"
-        elif cpu_root != root_ref:
-            raise SystemExit("CPU restatement disagrees with its golden: %s vs %s" % (cpu_root, root_ref))
-    if root_ref is not None:
-        for x in results + [tr]:
-            if x.root_line != root_ref:
-                raise SystemExit("WRONG ROOT: %s, the CPU restatement gives %s" % (x.root_line, root_ref))
-
-    line = {
-        "metric": "positions solved/sec (node)",
-        "value": P * args.steps / elapsed,
-        "unit": "positions/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": ("u%d order-form words, integer (%s table: keys implicit in the slot)" % (word_bits, layout)
-                  if layout in ("dense", "planes") else "u64 keys / u32 words, integer"),
-        "data": "synthetic: sum of Four-To-One heaps, fully determined state space",
-        "config": {"workload": workload,
-                   "positions_per_gpu": P // world, "edges_per_gpu": E // world,
-                   "levels": r.levels, "root": r.root_line, "root_checked_against": root_src,
-                   "layout": layout,
-                   "parallelism": ((("row deal: heap 1 in 32-row slabs x%d, each level's last two rows per plane "
-                                     "streamed to the next rank" if layout == "planes" and heaps[1] != 31 else
-                                     "staged pipeline: one block of the top heap per rank x%d, halo rows "
-                                     "streamed to the next rank" if layout == "planes" else
-                                     "round-robin top-heap blocks x%d, one halo exchange per level") % world
-                                    + ", %s" % ("host-staged (gloo, all ranks on one GPU: rehearsal, not a "
-                                                "performance figure)" if host else "RCCL"))
-                                   if world > 1 else "1 GPU")},
-        "roofline": roof,
-        "step_issue": ("queued solves (gm_solver_solve_async, <= %d outstanding): back to back on the GPU, "
-                       "each collected and checked; solve_wall = one solve's device span" % QDEPTH
-                       if queued else "one blocking solve() per step"),
-        "phase_ms": {"forward": r.ms_forward, "backward": r.ms_backward,
-                     "solve_wall": r.ms_total,
-                     "expand_kernels": tr.ms_expand_kernels,
-                     "resolve_kernels": tr.ms_resolve_kernels},
-    }
-    if rank == 0 and world == 1 and not args.no_keyed:
-        del solver
-        torch.cuda.empty_cache()
-        line["keyed"] = keyed_record("cuda:%d" % local)
-    if cpu is not None:
-        line["cpu_baseline"] = cpu
-    if rank == 0:
-        print(json.dumps(line), flush=True)
-    if dist is not None:
-        dist.destroy_process_group()
+    return roof, tr
 
 
 if __name__ == "__main__":

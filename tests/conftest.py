@@ -8,16 +8,11 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-REFERENCE = "/root/reference"
 
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs an MI355X (gfx950) GPU")
     config.addinivalue_line("markers", "slow: long-running")
-
-
-def has_reference():
-    return os.path.isdir(os.path.join(REFERENCE, "test_games"))
 
 
 @pytest.fixture(scope="session")

@@ -77,6 +77,42 @@ def test_kernel_names_come_from_the_library():
     assert _lib.PULL_KERNELS[1] == "k_dense_pull_words"
 
 
+def test_dump_outputs_writes_a_fixed_sample_as_float_arrays(tmp_path):
+    """--dump-outputs: the result scalars, a seeded sample of table words
+    (key 0 and the root first; the same keys every run) and the whole-table
+    fingerprint, as float32 / float64 .npy well under 64 MB."""
+    import types
+    import numpy as np
+    P = 1 << 30
+    asked = []
+
+    def query(keys):
+        asked.append(keys.copy())
+        return ((keys % 3).astype(np.uint32) | ((keys % 127).astype(np.uint32) << 2))
+
+    solver = types.SimpleNamespace(
+        world=1, query=query,
+        checksum=lambda: {"checksum": "0123456789abcdef", "positions": P, "win": 7, "loss": 5, "tie": 0, "draw": 0})
+    res = types.SimpleNamespace(root_value=1, root_remoteness=126, positions=P, edges=12280922112, primitives=1,
+                                levels=187, max_level_width=3, extra={"word_bits": 16})
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), solver, res, P)
+    np.testing.assert_array_equal(asked[0], asked[1])
+    keys = asked[0]
+    assert len(keys) == bench.DUMP_SAMPLE and keys[0] == 0 and keys[1] == P - 1 and int(keys.max()) < P
+    out = {f[:-4]: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(out) == ["result", "sample_keys", "sample_remoteness", "sample_value", "table_fingerprint"]
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert sum(a.nbytes for a in out.values()) < 64 << 20
+    np.testing.assert_array_equal(out["sample_keys"], keys.astype(np.float64))
+    np.testing.assert_array_equal(out["sample_value"], keys % 3)
+    np.testing.assert_array_equal(out["sample_remoteness"], keys % 127)
+    assert out["result"].tolist() == [1, 126, P, 12280922112, 1, 187, 3, 16]
+    assert out["table_fingerprint"].tolist() == [0x0123, 0x4567, 0x89ab, 0xcdef, P, 7, 5, 0, 0]
+    for f in os.listdir(tmp_path / "a"):
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+
+
 def test_planes_traffic_is_a_launch_weighted_mean(monkeypatch):
     """The PMC pass may hold several solves: the bench's PLANES traffic is
     bytes per launch over the pass's own launches, not scaled by them."""

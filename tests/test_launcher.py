@@ -2,9 +2,10 @@
 their device descriptors and pass the descriptor-vs-module replay check
 (gamesmanmpi_amd/solver_launcher.py, games.spec_for_module/verify).
 
-CPU tests load the reference's OWN game files (only where /root/reference
-exists; third-party imports they need come from tests/golden/refstubs).  The
-GPU test runs the launcher end to end on a game file shipped here."""
+CPU tests replay the reference's OWN game files from their recorded answers
+(tests/recorded_games.py over tests/golden/refgames, written by
+tests/golden/make_refgames.py from the reference's modules).  The GPU test
+runs the launcher end to end on a game file shipped here."""
 import importlib.util
 import io
 import os
@@ -15,7 +16,8 @@ from contextlib import redirect_stdout
 import numpy as np
 import pytest
 
-from conftest import REFERENCE, ROOT, has_reference
+from conftest import ROOT
+from recorded_games import RecordedGame, recorded_json
 
 STUBS = os.path.join(ROOT, "tests", "golden", "refstubs")
 OWN_SUM = os.path.join(ROOT, "gamesmanmpi_amd", "games", "sum_four_to_one.py")
@@ -55,23 +57,21 @@ def test_compat_utils_semantics():
     assert sl.COMPAT.endswith("compat")
 
 
-@pytest.mark.skipif(not has_reference(), reason="reference not mounted")
 def test_compat_utils_match_reference_module():
-    spec = importlib.util.spec_from_file_location(
-        "ref_utils", os.path.join(REFERENCE, "src", "utils.py"))
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
+    ref = recorded_json("src_utils")
     spec = importlib.util.spec_from_file_location(
         "compat_utils2", os.path.join(ROOT, "gamesmanmpi_amd", "compat", "src",
                                       "utils.py"))
     ours = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(ours)
-    for name in ("WIN", "LOSS", "TIE", "DRAW", "UNDECIDED", "PRIMITIVES",
-                 "PRIMITIVE_REMOTENESS", "UNKNOWN_REMOTENESS", "STATE_MAP"):
-        assert getattr(ours, name) == getattr(ref, name), name
+    for name in ("WIN", "LOSS", "TIE", "DRAW", "UNDECIDED",
+                 "PRIMITIVE_REMOTENESS", "UNKNOWN_REMOTENESS"):
+        assert getattr(ours, name) == ref["constants"][name], name
+    assert list(ours.PRIMITIVES) == ref["constants"]["PRIMITIVES"]
+    assert sorted([k, v] for k, v in ours.STATE_MAP.items()) == ref["STATE_MAP"]
     for x in range(5):
-        assert ours.negate(x) == ref.negate(x)
-        assert ours.to_str(x) == ref.to_str(x)
+        assert ours.negate(x) == ref["negate"][x]
+        assert ours.to_str(x) == ref["to_str"][x]
 
 
 REF_GAMES = [
@@ -82,25 +82,35 @@ REF_GAMES = [
     ("toot_and_otto_bitstring.py", {"length": 4, "height": 3}),
     ("othello_bit_new.py", {"length": 4, "height": 4}),       # config 5 size
 ]
+RECORDINGS = {"toot_and_otto_bitstring.py": "toot_%dx%d", "othello_bit_new.py": "othello_%dx%d"}
 
 
-@pytest.mark.skipif(not has_reference(), reason="reference not mounted")
+def _recorded(fname, **overrides):
+    """The reference's game file `fname`, loaded with `overrides`, from its
+    recording; validated like a loaded game file."""
+    from gamesmanmpi_amd import solver_launcher as sl
+    case = os.path.splitext(fname)[0]
+    if fname in RECORDINGS:
+        case = RECORDINGS[fname] % (overrides.get("length", 6), overrides.get("height", 4))
+    mod = RecordedGame(case)
+    assert mod.overrides == overrides
+    sl.validate(mod)
+    return mod
+
+
 @pytest.mark.parametrize("fname,overrides", REF_GAMES)
 def test_reference_game_files_map_and_verify(fname, overrides):
     from gamesmanmpi_amd.games import spec_for_module
-    mod = _load(os.path.join(REFERENCE, "test_games", fname), "gm_launch_test",
-                **overrides)
+    mod = _recorded(fname, **overrides)
     spec = spec_for_module(mod, os.path.splitext(fname)[0])
     assert spec.verify(mod, samples=150) == 150
 
 
-@pytest.mark.skipif(not has_reference(), reason="reference not mounted")
 def test_modified_game_file_is_refused():
     """A game file whose rules differ from its descriptor must not be
     silently solved with stale rules."""
     from gamesmanmpi_amd.games import spec_for_module
-    mod = _load(os.path.join(REFERENCE, "test_games", "four_to_one.py"),
-                "gm_launch_mod")
+    mod = _recorded("four_to_one.py")
     mod.gen_moves = lambda x: [-1]  # a different game
     spec = spec_for_module(mod, "four_to_one")
     with pytest.raises(ValueError):

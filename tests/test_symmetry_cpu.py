@@ -1,14 +1,13 @@
 """Symmetry hooks on the host (include/gamesman.h gm_symmetry; SURVEY.md
 §8f rank 4): the descriptor's player_flip is a level-preserving involution,
 canonical keys are orbit minima, games without symmetry_functions() refuse
-the hook, and -- where the reference is mounted -- the reference module's
-own symmetry_functions() agree with the descriptor's key maps."""
-import os
-
+the hook, and the reference module's own symmetry_functions() (from their
+recorded answers, tests/recorded_games.py) agree with the descriptor's key
+maps."""
 import numpy as np
 import pytest
 
-from conftest import CASES, REFERENCE, has_reference, load_table
+from conftest import CASES, load_table
 
 
 def test_flip_is_a_level_preserving_involution():
@@ -38,12 +37,10 @@ def test_games_without_symmetry_functions_refuse_the_hook():
             GameSpec(name, params)
 
 
-@pytest.mark.skipif(not has_reference(), reason="reference not mounted")
 def test_reference_symmetry_functions_match_descriptor():
-    from test_launcher import _load
+    from test_launcher import _recorded
     from gamesmanmpi_amd.games import GameSpec
-    mod = _load(os.path.join(REFERENCE, "test_games", "othello_bit_new.py"),
-                "gm_sym_test", length=4, height=4)
+    mod = _recorded("othello_bit_new.py", length=4, height=4)
     spec = GameSpec("othello_bit_new", "length=4,height=4,symmetry=1")
     assert spec.verify_symmetries(mod, samples=150) == 150
     assert spec.verify(mod, samples=150) == 150

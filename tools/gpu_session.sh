@@ -5,7 +5,7 @@
 # steps:
 #   tests[:EXPR]   python -m pytest tests -m gpu (-k EXPR)       -> TAG_gpu_tests.log
 #   smoke          __graft_entry__.smoke()                        -> TAG_smoke.log
-#   bench          python bench.py --steps 20 --warmup 5          -> TAG_bench.json
+#   bench          python bench.py --full --steps 20 --warmup 5   -> TAG_bench.json
 #   prof           rocprofv3 --kernel-trace --stats of a short bench -> TAG_prof/
 #   pmc            the PMC passes of one bench step (tools/pmc_passes.sh) -> TAG_pmc/, TAG_pmc_traffic.json
 #   atomics        toot 6x4 atomic counters (tools/pmc_atomics.sh)    -> TAG_atomics.json
@@ -33,12 +33,12 @@ for step in "$@"; do
         || fail smoke ${o}_smoke.log
       tail -1 ${o}_smoke.log ;;
     bench)
-      timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 > ${o}_bench.json 2> ${o}_bench.err \
+      timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 5 > ${o}_bench.json 2> ${o}_bench.err \
         || fail bench ${o}_bench.err
       cat ${o}_bench.json ;;
     prof)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d ${o}_prof -o run \
-        -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > ${o}_prof.log 2>&1 || fail prof ${o}_prof.log
+        -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > ${o}_prof.log 2>&1 || fail prof ${o}_prof.log
       python3 tools/kstats.py $(find ${o}_prof -name '*kernel_stats.csv' | head -1) | head -20 ;;
     pmc)  # + the per-launch traffic bench.py reads (copy it to profiles/pmc_traffic.json)
       bash tools/pmc_passes.sh ${o}_pmc > ${o}_pmc.log 2>&1 || fail pmc ${o}_pmc.log

@@ -8,7 +8,7 @@ set -e
 out=${1:-gpurun_out/pmc}
 shift || true
 args=("$@")
-[ ${#args[@]} -eq 0 ] && args=(--steps 1 --warmup 0 --no-cpu-baseline)
+[ ${#args[@]} -eq 0 ] && args=(--full --steps 1 --warmup 0 --no-cpu-baseline)
 export TMPDIR=/tmp
 mkdir -p "$out"
 pass() {
