@@ -662,7 +662,7 @@ static int plane_lists(gm_solver* s, const PlaneShape& ps, std::vector<uint8_t>&
   }
   // per level, the planes that read a halo plane (top values gB, gB + 1 of
   // blocks with a predecessor) last: the launch can be split into an own
-  // part and a boundary part that waits for the exchange (run_planes)
+  // part and a boundary part that waits for the exchange (plane_levels_piped)
   s->pbnd.assign((size_t)S + 1, 0);
   auto reads_halo = [](const PlaneEntry& e) { return e.top1 < kPlaneLocal || e.top2 < kPlaneLocal; };
   for (uint32_t l = 0; l <= S; l++) {
@@ -713,35 +713,10 @@ static int plane_setup(gm_solver* s, const gm_buffers* buf) {
     // padded to whole visits; the level's visits cut into 8 contiguous XCD
     // chunks, a chunk dealt round robin over its XCD's sequences
     const uint32_t* L = (const uint32_t*)lb.data();
-    // (lab knob GM_PLANE_FLOW_SEQ: sequences per XCD, 1..kPlaneFlowSeqMax; A/B)
-    uint32_t nseq = kPlaneFlowSeq;
-    if (const char* e = lab_env("GM_PLANE_FLOW_SEQ")) nseq = std::max(1u, std::min(kPlaneFlowSeqMax, (uint32_t)atoi(e)));
-    const uint32_t nq = 8 * nseq;
+    const uint32_t nseq = kPlaneFlowSeq, nq = 8 * nseq;
     std::vector<std::vector<uint32_t>> qv(nq);
-    // (lab knob GM_PLANE_FLOW_DEAL=1: XCD x takes the planes whose top outer
-    // digit lies in slab x of 8 -- the same XCD for a plane at every level,
-    // so neighbours along the other digits share its L2 -- instead of an
-    // even chunk of every level; A/B)
-    const char* deal_e = lab_env("GM_PLANE_FLOW_DEAL");
-    const bool slabs = deal_e && atoi(deal_e) == 1 && ps.g.no >= 2;
-    const uint32_t tb = ps.g.base[ps.g.no > 0 ? ps.g.no - 1 : 0];
     for (uint32_t l = 0; l <= ps.S; l++) {
       std::vector<uint32_t> v(L + s->ploff[l], L + s->ploff[(size_t)l + 1]);
-      if (slabs) {
-        std::vector<std::vector<uint32_t>> xv(8);
-        for (uint32_t P : v) {
-          const uint32_t top = (uint32_t)((P / ps.g.stride[ps.g.no - 1]) % tb);
-          xv[std::min(7u, top * 8u / tb)].push_back(P);
-        }
-        for (uint32_t x = 0; x < 8; x++) {
-          while (xv[x].size() % 4) xv[x].push_back(kPlaneAbsent);
-          for (u64 i = 0; i < xv[x].size() / 4; i++) {
-            auto& q = qv[x + 8 * (i % nseq)];
-            q.insert(q.end(), xv[x].begin() + 4 * i, xv[x].begin() + 4 * i + 4);
-          }
-        }
-        continue;
-      }
       while (v.size() % 4) v.push_back(kPlaneAbsent);
       const u64 nv = v.size() / 4, chunk = (nv + 7) / 8;
       for (u64 x = 0; x < 8; x++)
@@ -780,8 +755,7 @@ static int plane_setup(gm_solver* s, const gm_buffers* buf) {
         occ = 0;
     });
     const u64 cus = (u64)launch_grid() / 8;
-    u64 bpc = std::min<u64>(kPlaneFlowBlocksPerCU, (u64)std::max(occ, 0));
-    if (const char* e = lab_env("GM_PLANE_FLOW_BPC")) bpc = std::min<u64>(bpc, (u64)std::max(1, atoi(e)));  // (lab A/B)
+    const u64 bpc = std::min<u64>(kPlaneFlowBlocksPerCU, (u64)std::max(occ, 0));
     const u64 blocks = cus * bpc / nq * nq;
     s->pflow_grid = (uint32_t)blocks;
     s->pflow_ok = blocks >= nq;
@@ -999,18 +973,11 @@ static void plane_reach_launch(gm_solver* s, hipStream_t stream = nullptr) {
 // power-of-two bases, levels (l, l + 1) both wider than a one-workgroup run
 // and both at most kPlanePairMax planes (the pair's redundant first visits
 // grow with the width: 14 pairs over levels 4-17 and 107-120 of the 2^30
-// bench table at the default).  (lab knob GM_PLANE_PAIR_MAX; 0: no pairs)
+// bench table).  0: this solver takes no pairs
 constexpr u64 kPlanePairMax = 1200;
-// (A/B, GM_PLANE_FWD=3) the forward's side-stream start: the first level
-// past the widest with at most this many planes (run_planes)
-constexpr u64 kPlaneFwdTail = 2048;
 static u64 plane_pair_max(const gm_solver* s) {
-  static const long long v = [] {
-    const char* e = lab_env("GM_PLANE_PAIR_MAX");
-    return e ? atoll(e) : -1ll;
-  }();
   const bool ok = s->world <= 1 && s->pform == 1 && !plane_x1(s) && s->pg.no >= 1 && s->pg.no <= 4 && s->pg.pow2;
-  return !ok ? 0 : v >= 0 ? (u64)v : kPlanePairMax;
+  return ok ? kPlanePairMax : 0;
 }
 // levels l and l + 1 of a one-table solve in one launch
 static void plane_pair_launch(gm_solver* s, uint32_t l) {
@@ -1516,15 +1483,86 @@ static int plane_result(const std::vector<gm_solver*>& ss, const u64* red, gm_re
   return 0;
 }
 
-static int run_planes(std::vector<gm_solver*> ss, gm_result* out, bool async) {
-  gm_solver* s0 = ss[0];
-  const Desc& d = s0->d;
-  const int T = d.max_levels;
-  const uint32_t S = s0->pS;
-  // mode 2: a group on ONE stream; mode 4: a group whose shards have their
-  // own streams -- the rehearsal of mode 1's staged schedule
+// The events made for ONE solve (kernel timing; the fork and joins of a
+// group on its own streams): destroyed on every return path.  The persistent
+// ones (pse, the ring slots', pev) stay with the solver.
+struct PlaneSolveEvents {
+  std::vector<hipEvent_t> kr;             // per-level start / stop (shard 0's launches)
+  hipEvent_t kx[2] = {nullptr, nullptr};  // around the forward's launches
+  hipEvent_t ef = nullptr;                // mode 4: the shards' streams fork from the solve stream
+  std::vector<hipEvent_t> ej;             // mode 4: and join it, one per shard
+  PlaneSolveEvents() = default;
+  PlaneSolveEvents(const PlaneSolveEvents&) = delete;
+  PlaneSolveEvents& operator=(const PlaneSolveEvents&) = delete;
+  ~PlaneSolveEvents() {
+    for (hipEvent_t e : kr) drop(e);
+    for (hipEvent_t e : ej) drop(e);
+    drop(kx[0]), drop(kx[1]), drop(ef);
+  }
+  static void drop(hipEvent_t e) {
+    if (e) (void)hipEventDestroy(e);
+  }
+};
+
+// One solve: what plane_solve_begin decides, read by the schedule that runs
+struct PlaneSolve {
+  std::vector<gm_solver*>& ss;
+  gm_solver* s0;
+  bool async;  // queued (gm_solver_solve_async)
+  // 0: one table; 1: one shard per process, RCCL; 2: a group on ONE stream;
+  // 3: one shard per process, host-staged transport; 4: a group whose shards
+  // have their own streams -- the rehearsal of mode 1's staged schedule
+  int mode = 0;
+  int T = 0, first = 0, stop = 0;  // levels; the steps [first, stop) of 2T (gm_solver_set_steps, one table only)
+  uint32_t S = 0;                  // largest plane level
+  bool timing = false;             // GM_F_KERNEL_TIMING (whole blocking solves)
+  bool staged = false;             // shards: the staged deal (else level-synchronous)
+  bool flow = false;               // the backward as ONE launch (k_plane_flow)
+  bool overlap = false;            // the forward on the side stream fs, beside the per-level backward
+  bool lite = false;               // records only its start and its completion
+  hipStream_t st = nullptr, fs = nullptr;  // the solve stream; the forward's
+  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, etail = nullptr;  // start, forward end, backward end, forward start
+  PlaneSolveEvents ev;
+  u64* flow_host = nullptr;  // the one-launch solve's reduction words (pinned)
+  u64 nlaunch = 0;           // resolve launches of this solve (shard 0's)
+  std::chrono::steady_clock::time_point t0;
+  bool whole() const { return first == 0 && stop == 2 * T; }
+  // kernel timing of level-synchronous shards: an event pair around each
+  // level's launches (exchanges sit between them); else one pair around the
+  // whole backward (no events between launches: they would add their own
+  // gaps to what they time)
+  bool per_level() const { return timing && mode != 0 && !staged; }
+};
+
+// mode 4: the shards' own streams fork from st after e0 and join it before
+// e1, fork again for the backward and join before e2 (other modes: every
+// shard runs on st)
+static int plane_fork(PlaneSolve& c) {
+  if (c.mode != 4) return 0;
+  HIPCHK(hipEventRecord(c.ev.ef, c.st));
+  for (gm_solver* s : c.ss)
+    if (s->stream != c.st) HIPCHK(hipStreamWaitEvent(s->stream, c.ev.ef, 0));
+  return 0;
+}
+static int plane_join(PlaneSolve& c) {
+  if (c.mode != 4) return 0;
+  for (size_t g = 0; g < c.ss.size(); g++)
+    if (c.ss[g]->stream != c.st) {
+      HIPCHK(hipEventRecord(c.ev.ej[g], c.ss[g]->stream));
+      HIPCHK(hipStreamWaitEvent(c.st, c.ev.ej[g], 0));
+    }
+  return 0;
+}
+
+// The prologue of every solve: mode and group checks, the steps, the resume
+// and plan checks, the events, and which schedule runs
+static int plane_solve_begin(PlaneSolve& c) {
+  std::vector<gm_solver*>& ss = c.ss;
+  gm_solver* s0 = c.s0;
+  c.T = s0->d.max_levels;
+  c.S = s0->pS;
   const bool own_streams = ss.size() > 1 && ss[1]->stream != s0->stream;
-  const int mode = s0->world <= 1 ? 0 : ss.size() != 1 ? (own_streams ? 4 : 2) : s0->xfer ? 3 : 1;
+  const int mode = c.mode = s0->world <= 1 ? 0 : ss.size() != 1 ? (own_streams ? 4 : 2) : s0->xfer ? 3 : 1;
   if (mode == 1 && !s0->comm) return fail(GM_EINVAL, "shard %d/%d has no communicator (gm_solver_comm_init)", s0->rank, s0->world);
   if (mode == 2 || mode == 4) {
     if ((int)ss.size() != s0->world) return fail(GM_EINVAL, "group solve needs all %d shards", s0->world);
@@ -1538,364 +1576,317 @@ static int run_planes(std::vector<gm_solver*> ss, gm_result* out, bool async) {
     if (mode == 4 && !s0->pstage_k)
       return fail(GM_EINVAL, "shards on their own streams rehearse the staged deal only (this shape is level-synchronous)");
   }
-  const int first = mode == 0 ? (int)s0->step_first : 0;
-  const int stop = mode == 0 && s0->step_stop ? (int)s0->step_stop : 2 * T;
+  c.first = mode == 0 ? (int)s0->step_first : 0;
+  c.stop = mode == 0 && s0->step_stop ? (int)s0->step_stop : 2 * c.T;
   s0->step_first = s0->step_stop = 0;
-  const bool timing = (s0->flags & GM_F_KERNEL_TIMING) && first == 0 && stop == 2 * T;
-  if (async && (mode != 0 || first != 0 || stop != 2 * T || timing))
+  c.timing = (s0->flags & GM_F_KERNEL_TIMING) && c.whole();
+  if (c.async && (mode != 0 || !c.whole() || c.timing))
     return fail(GM_EINVAL, "queued solves: one-table PLANES full solves without kernel timing only");
-  hipStream_t st = s0->stream;
-  if (first > 0) {
+  c.st = s0->stream;
+  if (c.first > 0) {
     uint32_t wb = 0;
     HIPCHK(hipMemcpy(&wb, &s0->st->word_bits, sizeof wb, hipMemcpyDeviceToHost));
     if (wb != s0->pmark())
       return fail(GM_EINVAL, "resume: the scratch holds no %u-bit%s planes solve", 8 * s0->pwb,
                   s0->pform == 3 ? " relative" : "");
   }
-  const bool staged = mode != 0 && s0->pstage_k;
+  c.staged = mode != 0 && s0->pstage_k;
   for (gm_solver* s : ss) {
     s->defer_rc = 0;
     s->defer_msg.clear();
   }
   if (mode != 0 && !s0->halo_ok) {
-    int rc = staged ? plane_check_stage(ss, mode, st) : plane_check_plan(ss, mode, st);
+    int rc = c.staged ? plane_check_stage(ss, mode, c.st) : plane_check_plan(ss, mode, c.st);
     if (rc) return rc;
   }
-  std::vector<hipEvent_t> ev;
-  auto new_event = [&](hipEvent_t* e) -> int {
-    HIPCHK(hipEventCreate(e));
-    ev.push_back(*e);
-    return 0;
-  };
-  auto cleanup = [&]() {
-    for (auto e : ev) (void)hipEventDestroy(e);
-  };
-  // the solve's three timing events live with the solver (created once: a
-  // create + destroy per event per solve was host time between solves); a
-  // queued solve (gm_solver_solve_async) uses its ring slot's own
-  hipEvent_t e0, e1, e2, etail;
+  // the solve's timing events live with the solver (created once: a create +
+  // destroy per event per solve was host time between solves); a queued
+  // solve uses its ring slot's own
   {
-    hipEvent_t* se = async ? s0->pring[s0->pq_next % kPlaneRing].ev : s0->pse;
+    hipEvent_t* se = c.async ? s0->pring[s0->pq_next % kPlaneRing].ev : s0->pse;
     for (int i = 0; i < 3; i++)
       if (!se[i]) HIPCHK(hipEventCreate(&se[i]));
     if (!se[4]) HIPCHK(hipEventCreate(&se[4]));
-    e0 = se[0], e1 = se[1], e2 = se[2], etail = se[4];
+    c.e0 = se[0], c.e1 = se[1], c.e2 = se[2], c.etail = se[4];
   }
-  std::vector<hipEvent_t> kr;  // per-level start/stop (shard 0's launches)
-  hipEvent_t kx[2];
-  if (timing) {
-    kr.resize(2 * ((size_t)S + 1));
-    for (auto& e : kr)
-      if (new_event(&e)) return GM_EHIP;
-    if (new_event(&kx[0]) || new_event(&kx[1])) return GM_EHIP;
+  if (c.timing) {
+    c.ev.kr.assign(2 * ((size_t)c.S + 1), nullptr);
+    for (hipEvent_t& e : c.ev.kr) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventCreate(&c.ev.kx[0]));
+    HIPCHK(hipEventCreate(&c.ev.kx[1]));
   }
-  // mode 4: the shards' own streams fork from st after e0 and join it
-  // before e1, fork again for the backward and join before e2 (other modes:
-  // every shard runs on st)
-  hipEvent_t ef = nullptr;
-  std::vector<hipEvent_t> ej;
   if (mode == 4) {
-    if (new_event(&ef)) return GM_EHIP;
-    ej.resize(ss.size());
-    for (auto& e : ej)
-      if (new_event(&e)) return GM_EHIP;
+    HIPCHK(hipEventCreate(&c.ev.ef));
+    c.ev.ej.assign(ss.size(), nullptr);
+    for (hipEvent_t& e : c.ev.ej) HIPCHK(hipEventCreate(&e));
   }
-  auto fork = [&]() -> int {
-    if (mode != 4) return 0;
-    HIPCHK(hipEventRecord(ef, st));
-    for (gm_solver* s : ss)
-      if (s->stream != st) HIPCHK(hipStreamWaitEvent(s->stream, ef, 0));
-    return 0;
-  };
-  auto join = [&]() -> int {
-    if (mode != 4) return 0;
-    for (size_t g = 0; g < ss.size(); g++)
-      if (ss[g]->stream != st) {
-        HIPCHK(hipEventRecord(ej[g], ss[g]->stream));
-        HIPCHK(hipStreamWaitEvent(st, ej[g], 0));
-      }
-    return 0;
-  };
-  // One table, whole solve: the forward -- state and count-slot resets,
-  // reach map + counts -- runs on a side stream BESIDE the backward, which
-  // never reads any of it (a plane's words follow from its neighbours'
-  // words alone); the finish kernel waits for both.  The reach launch then
-  // overlaps the first, narrow plane levels instead of preceding them.
-  // A QUEUED solve (gm_solver_solve_async) runs its forward on the solve
-  // stream before the backward instead: with the next solves already in the
-  // queues, a side-stream forward made every queued solve 0.10-0.14 ms
-  // longer on the device, whether it started with the backward (1.37-1.46
-  // vs 1.27-1.31 ms per 2^30 solve) or at its narrow tail (1.40 ms);
-  // profiles/r06/forward_placement_probe.txt.  (lab knob GM_PLANE_FWD:
-  // 1 = always on the solve stream, 2 = always on the side stream from the
-  // start, 3 = always on the side stream from the narrow tail -- the first
-  // level past the widest with <= kPlaneFwdTail planes; A/B)
-  static const int fwd_mode = [] {
-    const char* e = lab_env("GM_PLANE_FWD");
-    return e ? atoi(e) : 0;
-  }();
   // one table, whole solve: the backward as ONE launch (k_plane_flow,
-  // gm_plane.h) -- GM_F_PLANE_LEVELS keeps the per-level launches (A/B; lab
-  // knob GM_PLANE_FLOW=0 too), and partial / resumed solves take them
-  static const bool flow_knob = [] {
-    const char* e = lab_env("GM_PLANE_FLOW");
-    return !(e && atoi(e) == 0);
-  }();
-  const bool flow = mode == 0 && s0->pflow_ok && first == 0 && stop == 2 * T && flow_knob &&
-                    !(s0->flags & (GM_F_PLANE_LEVELS | GM_F_PLANE_X1));
-  // (the one-launch backward runs after the forward on the solve stream:
-  // the forward's state reset must not race its error bit)
-  const bool overlap = mode == 0 && first == 0 && stop == 2 * T && !timing && fwd_mode != 1 &&
-                       (!async || fwd_mode >= 2) && !flow;
-  uint32_t fwd_at = 0;  // the level whose launch the side-stream forward is enqueued after
-  if (overlap && fwd_mode == 3) {
-    uint32_t pk = 0;
-    for (uint32_t l = 0; l <= S; l++)
-      if (s0->ploff[(size_t)l + 1] - s0->ploff[l] > s0->ploff[(size_t)pk + 1] - s0->ploff[pk]) pk = l;
-    fwd_at = S;
-    for (uint32_t l = pk + 1; l <= S; l++)
-      if (s0->ploff[(size_t)l + 1] - s0->ploff[l] <= kPlaneFwdTail) {
-        fwd_at = l;
-        break;
-      }
-  }
-  hipStream_t fs = st;  // the forward's stream
-  if (overlap) {
-    if (!s0->cstream) {
-      HIPCHK(hipStreamCreateWithFlags(&s0->cstream, hipStreamNonBlocking));
-    }
-    fs = s0->cstream;
+  // gm_plane.h) -- GM_F_PLANE_LEVELS keeps the per-level launches (A/B), and
+  // partial / resumed solves take them
+  c.flow = mode == 0 && s0->pflow_ok && c.whole() && !(s0->flags & (GM_F_PLANE_LEVELS | GM_F_PLANE_X1));
+  // One table, whole solve, per-level backward: the forward -- state and
+  // count-slot resets, reach map + counts -- runs on a side stream BESIDE the
+  // backward, which never reads any of it (a plane's words follow from its
+  // neighbours' words alone); the finish kernel waits for both.  The reach
+  // launch then overlaps the first, narrow plane levels instead of preceding
+  // them.  A QUEUED solve runs its forward on the solve stream before the
+  // backward instead: with the next solves already in the queues, a
+  // side-stream forward made every queued solve 0.10-0.14 ms longer on the
+  // device, whether it started with the backward (1.37-1.46 vs 1.27-1.31 ms
+  // per 2^30 solve) or at its narrow tail (1.40 ms);
+  // profiles/r06/forward_placement_probe.txt.  So does the one-launch
+  // backward: the forward's state reset must not race its error bit.
+  c.overlap = mode == 0 && c.whole() && !c.timing && !c.async && !c.flow;
+  c.fs = c.st;
+  if (c.overlap) {
+    if (!s0->cstream) HIPCHK(hipStreamCreateWithFlags(&s0->cstream, hipStreamNonBlocking));
+    c.fs = s0->cstream;
   }
   // a queued one-launch solve records only its start and its completion:
   // the forward has no launch of its own and every timing marker between
   // solves is a gap on the device (the trace: ~20 us between one solve's
   // finish and the next launch); ms_forward 0, ms_backward = the whole span
-  // (lab knob GM_PLANE_FLOW_LITE=0: all five events; A/B)
-  static const bool lite_knob = [] {
-    const char* e = lab_env("GM_PLANE_FLOW_LITE");
-    return !(e && atoi(e) == 0);
-  }();
-  const bool lite = async && flow && lite_knob;
-  if (async) s0->pring[s0->pq_next % kPlaneRing].lite = lite;
-  auto t0 = std::chrono::steady_clock::now();
-  HIPCHK(hipEventRecord(e0, st));
-  if (fork()) return GM_EHIP;
-  auto issue_forward = [&]() -> int {
-    if (first == 0) {
-      for (gm_solver* s : ss) {
-        hipStream_t ws = overlap ? fs : s->stream;
-        // (a one-launch solve after another one: that launch left the state
-        // it needs clean -- error word 0, its count slots stored, not added)
-        if (flow && s->pflow_last) continue;
-        HIPCHK(hipMemsetAsync(s->st, 0, devstate_bytes(T), ws));
-        HIPCHK(hipMemsetAsync(s->bcount, 0, kCountSlots * sizeof(BlockCount), ws));
-        // the word width: written by k_plane_reach below (no reach: here)
-        if (stop == 0) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)&s->st->word_bits, (int)s->pmark(), 1, ws));
-      }
-      if (stop > 0) {
-        if (timing) HIPCHK(hipEventRecord(kx[0], st));
-        // (the one-launch backward writes the reach map and counts itself)
-        if (!flow)
-          for (gm_solver* s : ss) plane_reach_launch(s, overlap ? fs : nullptr);
-        if (timing && join()) return GM_EHIP;
-        if (timing) HIPCHK(hipEventRecord(kx[1], st));
-      }
+  c.lite = c.async && c.flow;
+  if (c.async) s0->pring[s0->pq_next % kPlaneRing].lite = c.lite;
+  return 0;
+}
+
+// The forward: state and count-slot resets, reach map + counts (the
+// one-launch backward writes those itself), on fs; e1 at its end
+static int plane_forward(PlaneSolve& c) {
+  int rc;
+  if (c.first == 0) {
+    for (gm_solver* s : c.ss) {
+      hipStream_t ws = c.overlap ? c.fs : s->stream;
+      // (a one-launch solve after another one: that launch left the state
+      // it needs clean -- error word 0, its count slots stored, not added)
+      if (c.flow && s->pflow_last) continue;
+      HIPCHK(hipMemsetAsync(s->st, 0, devstate_bytes(c.T), ws));
+      HIPCHK(hipMemsetAsync(s->bcount, 0, kCountSlots * sizeof(BlockCount), ws));
+      // the word width: written by k_plane_reach below (no reach: here)
+      if (c.stop == 0) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)&s->st->word_bits, (int)s->pmark(), 1, ws));
     }
-    HIPCHK(hipGetLastError());
-    if (join()) return GM_EHIP;
-    if (!lite) HIPCHK(hipEventRecord(e1, fs));  // overlap: the forward's end on its own stream
-    if (fork()) return GM_EHIP;
-    return 0;
-  };
-  // overlap: the forward (resets, reach map, counts) is enqueued on its side
-  // stream right after the backward's first launch (GM_PLANE_FWD=3: at its
-  // narrow tail, fwd_at), so the host's first enqueue is a resolve launch
-  // (the forward is read by the finish only)
-  bool fwd_pending = overlap;
-  if (!fwd_pending) {
-    if (!lite) HIPCHK(hipEventRecord(etail, st));  // (the forward's start: ms_forward)
-    const int rc = issue_forward();
-    if (rc) return rc;
+    if (c.stop > 0) {
+      if (c.timing) HIPCHK(hipEventRecord(c.ev.kx[0], c.st));
+      if (!c.flow)
+        for (gm_solver* s : c.ss) plane_reach_launch(s, c.overlap ? c.fs : nullptr);
+      if (c.timing && (rc = plane_join(c))) return rc;
+      if (c.timing) HIPCHK(hipEventRecord(c.ev.kx[1], c.st));
+    }
   }
-  // kernel timing: one table -- the backward is nothing but the resolve
-  // launches, so one event pair around all of them (no events between
-  // launches: they would add their own gaps to what they time); shards --
-  // a pair around each level's launches (exchanges sit between them)
-  const bool per_level = timing && mode != 0 && !staged;
-  // Shards (RCCL or in-process copies): each level's launch is split into
-  // the planes that read no halo plane -- the boundary slices the exchange
-  // sends are among them when blocks hold >= 4 top values -- and the ones
-  // that do.  Own part -> event -> exchange on the comm stream -> event;
-  // the boundary part of the NEXT level waits for it, so the exchange of
-  // level l overlaps the boundary part of l and the own part of l + 1.  The
-  // host-staged transport (mode 3) and blocks of < 4 values exchange in
-  // order.
-  bool pipe = (mode == 1 || mode == 2) && !staged;
-  if (s0->pg.B < 4 || (s0->flags & GM_F_SHARD_INORDER)) pipe = false;
-  hipStream_t cs = st;
-  hipEvent_t* PE = nullptr;  // [0, S]: own part of level l done; [S+1, 2S+2): exchange of l done
-  if (pipe) {
-    if (!s0->cstream) HIPCHK(hipStreamCreateWithFlags(&s0->cstream, hipStreamNonBlocking));
-    while (s0->pev.size() < 2 * ((size_t)S + 1)) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      s0->pev.push_back(e);
-    }
-    cs = s0->cstream;
-    PE = s0->pev.data();
+  HIPCHK(hipGetLastError());
+  if ((rc = plane_join(c))) return rc;
+  if (!c.lite) HIPCHK(hipEventRecord(c.e1, c.fs));  // overlap: the forward's end on its own stream
+  return plane_fork(c);
+}
+
+// The backward as ONE launch (one table, whole solve)
+static int plane_backward_flow(PlaneSolve& c) {
+  gm_solver* s0 = c.s0;
+  hipStream_t st = c.st;
+  // its finish writes the reduction words straight into pinned host memory:
+  // the queued slot's, or the solver's own for a blocking solve
+  u64** hp = c.async ? &s0->pring[s0->pq_next % kPlaneRing].host : &s0->phost;
+  if (!*hp) HIPCHK(hipHostMalloc((void**)hp, 8 * sizeof(u64), hipHostMallocDefault));
+  c.flow_host = *hp;
+  if (c.timing) HIPCHK(hipEventRecord(c.ev.kr[0], st));
+  PlaneFlow f = s0->pflow;
+  f.skip = kPlaneAbsent;
+  if (const char* e = lab_env("GM_FAULT_FLOW")) f.skip = (uint32_t)atoi(e);  // (read per solve)
+  f.mode = 0;
+  if (const char* e = lab_env("GM_PLANE_FLOW_MODE")) f.mode = (uint32_t)atoi(e);
+  f.epoch = ++s0->pflow.epoch;
+  if (f.epoch == 0) {  // (2^32 solves: the flags start over)
+    HIPCHK(hipMemsetAsync(f.flags, 0, (size_t)s0->pg.nplanes * 4, st));
+    f.epoch = s0->pflow.epoch = 1;
   }
-  int last_x = -1;  // last level exchanged on the comm stream
-  PlaneBatcher bat0(s0);  // one table: narrow levels in one-workgroup runs
-  const u64 pair_max = mode == 0 ? plane_pair_max(s0) : 0;  // and pairs of narrow levels in one launch
-  static const bool pair_runs = [] {  // (lab knob GM_PLANE_PAIR_RUNS=1: pairs replace the runs; A/B)
-    const char* e = lab_env("GM_PLANE_PAIR_RUNS");
-    return e && atoi(e) == 1;
-  }();
-  u64 nlaunch = 0;        // resolve launches of this solve (shard 0's)
-  s0->pflow_last = flow;
-  // the one-launch solve writes its reduction words straight into pinned host
-  // memory: the queued slot's, or the solver's own for a blocking solve
-  u64* flow_host = nullptr;
-  if (flow) {
-    u64** hp = async ? &s0->pring[s0->pq_next % kPlaneRing].host : &s0->phost;
-    if (!*hp) HIPCHK(hipHostMalloc((void**)hp, 8 * sizeof(u64), hipHostMallocDefault));
-    flow_host = *hp;
+  plane_no_dispatch(s0->pg.no, [&](auto NO) {
+    // (lab knob GM_PLANE_FLOW_PIPE=0: each visit polls before its rows;
+    // the pipelined form -- the next visit's polls mid-visit, tickets two
+    // ahead -- 1.017-1.021 vs 1.029-1.034 ms per step on one box,
+    // profiles/r06/flow_pipe_ab.txt; A/B)
+    if (const char* e = lab_env("GM_PLANE_FLOW_PIPE"); !(e && atoi(e) == 0))
+      hipLaunchKernelGGL((k_plane_flow<decltype(NO)::value, true>), dim3(s0->pflow_grid), dim3(256), 0, st,
+                         (uint8_t*)s0->ptab, s0->pg, s0->pzero, f, s0->pbits, s0->bcount, s0->st, s0->pmark());
+    else
+      hipLaunchKernelGGL((k_plane_flow<decltype(NO)::value, false>), dim3(s0->pflow_grid), dim3(256), 0, st,
+                         (uint8_t*)s0->ptab, s0->pg, s0->pzero, f, s0->pbits, s0->bcount, s0->st, s0->pmark());
+  });
+  c.nlaunch = 1;
+  if (c.timing) HIPCHK(hipEventRecord(c.ev.kr[2 * (size_t)c.S + 1], st));
+  return 0;
+}
+
+// Shards of the staged deal: plane_backward_staged, in the timing pair
+static int plane_backward_staged_solve(PlaneSolve& c) {
+  if (c.timing) HIPCHK(hipEventRecord(c.ev.kr[0], c.st));
+  int rc = plane_backward_staged(c.ss, c.mode, c.st, &c.nlaunch);
+  if (rc) return rc;
+  if (c.timing) {
+    if ((rc = plane_join(c))) return rc;
+    HIPCHK(hipEventRecord(c.ev.kr[2 * (size_t)c.S + 1], c.st));
   }
-  if (flow) {
-    if (timing) HIPCHK(hipEventRecord(kr[0], st));
-    PlaneFlow f = s0->pflow;
-    f.skip = kPlaneAbsent;
-    if (const char* e = lab_env("GM_FAULT_FLOW")) f.skip = (uint32_t)atoi(e);  // (read per solve)
-    f.mode = 0;
-    if (const char* e = lab_env("GM_PLANE_FLOW_MODE")) f.mode = (uint32_t)atoi(e);
-    f.epoch = ++s0->pflow.epoch;
-    if (f.epoch == 0) {  // (2^32 solves: the flags start over)
-      HIPCHK(hipMemsetAsync(f.flags, 0, (size_t)s0->pg.nplanes * 4, st));
-      f.epoch = s0->pflow.epoch = 1;
-    }
-    plane_no_dispatch(s0->pg.no, [&](auto NO) {
-      // (lab knob GM_PLANE_FLOW_PIPE=0: each visit polls before its rows;
-      // the pipelined form -- the next visit's polls mid-visit, tickets two
-      // ahead -- 1.017-1.021 vs 1.029-1.034 ms per step on one box,
-      // profiles/r06/flow_pipe_ab.txt; A/B)
-      if (const char* e = lab_env("GM_PLANE_FLOW_PIPE"); !(e && atoi(e) == 0))
-        hipLaunchKernelGGL((k_plane_flow<decltype(NO)::value, true>), dim3(s0->pflow_grid), dim3(256), 0, st,
-                           (uint8_t*)s0->ptab, s0->pg, s0->pzero, f, s0->pbits, s0->bcount, s0->st, s0->pmark());
-      else
-        hipLaunchKernelGGL((k_plane_flow<decltype(NO)::value, false>), dim3(s0->pflow_grid), dim3(256), 0, st,
-                           (uint8_t*)s0->ptab, s0->pg, s0->pzero, f, s0->pbits, s0->bcount, s0->st, s0->pmark());
-    });
-    nlaunch = 1;
-    if (timing) HIPCHK(hipEventRecord(kr[2 * (size_t)S + 1], st));
-  }
-  if (staged && stop == 2 * T) {
-    if (timing) HIPCHK(hipEventRecord(kr[0], st));
-    int rc = plane_backward_staged(ss, mode, st, &nlaunch);
-    if (rc) {
-      cleanup();
-      return rc;
-    }
-    if (timing && join()) return GM_EHIP;
-    if (timing) HIPCHK(hipEventRecord(kr[2 * (size_t)S + 1], st));
-  }
-  for (uint32_t l = 0; l <= S && !staged && !flow; l++) {
-    const int k = T + (int)l;
-    if (k < first) continue;
-    if (k >= stop) break;
-    if (per_level || (timing && l == 0)) HIPCHK(hipEventRecord(kr[2 * l], st));
-    if (mode == 0 && !per_level) {
-      const u64 n0 = s0->ploff[(size_t)l + 1] - s0->ploff[l];
-      const u64 n1 = l < S ? s0->ploff[(size_t)l + 2] - s0->ploff[(size_t)l + 1] : 0;
-      const u64 pmin = pair_runs ? 1 : bat0.narrow + 1;  // (pairs of run-narrow levels too: A/B)
-      if (l < S && k + 1 < stop && n0 >= pmin && n1 >= pmin && n0 <= pair_max && n1 <= pair_max) {
-        bat0.flush();  // levels l and l + 1 in one launch (k_plane_pair)
-        plane_pair_launch(s0, l);
-        bat0.launches++;
-        l++;
-      } else {
-        bat0.add(s0->ploff[l], s0->ploff[(size_t)l + 1], l, n1);
-      }
-      if (l == S) bat0.flush();
-      if (fwd_pending && bat0.launches > 0 && l >= fwd_at) {
-        fwd_pending = false;
-        bat0.flush();  // the side stream starts behind this level's launch
-        HIPCHK(hipEventRecord(etail, st));
-        HIPCHK(hipStreamWaitEvent(fs, etail, 0));
-        const int rc = issue_forward();
-        if (rc) return rc;
-      }
-    } else if (!pipe) {
-      for (gm_solver* s : ss) plane_launch(s, l);
-    } else {
-      for (gm_solver* s : ss) plane_launch(s, l, 1);
-      HIPCHK(hipEventRecord(PE[l], st));
-      HIPCHK(hipStreamWaitEvent(cs, PE[l], 0));
-    }
-    if (mode != 0) {
-      int rc = plane_exchange(ss, l, mode, cs);
-      if (rc) {
-        cleanup();
-        return rc;
-      }
-    }
-    if (pipe) {
-      HIPCHK(hipEventRecord(PE[S + 1 + l], cs));
-      last_x = (int)l;
-      // the boundary planes read the halos of levels l - 1 and l - 2
-      if (l >= 1) HIPCHK(hipStreamWaitEvent(st, PE[S + l], 0));
-      for (gm_solver* s : ss) plane_launch(s, l, 2);
-    }
-    if (per_level || (timing && l == S)) HIPCHK(hipEventRecord(kr[2 * l + 1], st));
-  }
-  bat0.flush();  // a stop inside a run
-  if (fwd_pending) {  // (not reached in the loop)
+  return 0;
+}
+
+// One table, level by level: narrow levels in one-workgroup runs
+// (PlaneBatcher), pairs of levels just wider than a run in one launch
+// (k_plane_pair), the rest one grid launch each.  overlap: the forward is
+// enqueued on its side stream right behind the backward's first launch, so
+// the host's first enqueue is a resolve launch (the forward is read by the
+// finish only).
+static int plane_levels_table(PlaneSolve& c) {
+  gm_solver* s0 = c.s0;
+  hipStream_t st = c.st;
+  const uint32_t S = c.S;
+  PlaneBatcher bat(s0);
+  const u64 pair_max = plane_pair_max(s0), pair_min = bat.narrow + 1;
+  bool fwd_pending = c.overlap;
+  auto forward_behind = [&]() -> int {
     fwd_pending = false;
-    HIPCHK(hipEventRecord(etail, st));
-    HIPCHK(hipStreamWaitEvent(fs, etail, 0));
-    const int rc = issue_forward();
+    HIPCHK(hipEventRecord(c.etail, st));
+    HIPCHK(hipStreamWaitEvent(c.fs, c.etail, 0));
+    return plane_forward(c);
+  };
+  if (c.timing) HIPCHK(hipEventRecord(c.ev.kr[0], st));
+  for (uint32_t l = 0; l <= S; l++) {
+    const int k = c.T + (int)l;
+    if (k < c.first) continue;
+    if (k >= c.stop) break;
+    const u64 n0 = s0->ploff[(size_t)l + 1] - s0->ploff[l];
+    const u64 n1 = l < S ? s0->ploff[(size_t)l + 2] - s0->ploff[(size_t)l + 1] : 0;
+    if (l < S && k + 1 < c.stop && n0 >= pair_min && n1 >= pair_min && n0 <= pair_max && n1 <= pair_max) {
+      bat.flush();  // levels l and l + 1 in one launch
+      plane_pair_launch(s0, l);
+      bat.launches++;
+      l++;
+    } else {
+      bat.add(s0->ploff[l], s0->ploff[(size_t)l + 1], l, n1);
+    }
+    if (l == S) bat.flush();
+    if (fwd_pending && bat.launches > 0) {
+      bat.flush();  // the side stream starts behind this level's launch
+      int rc = forward_behind();
+      if (rc) return rc;
+    }
+  }
+  bat.flush();  // a stop inside a run
+  if (fwd_pending) {  // (no launch in the loop)
+    int rc = forward_behind();
     if (rc) return rc;
   }
-  if (!staged && !flow) nlaunch = mode == 0 && !per_level ? bat0.launches : (u64)(S + 1) * (pipe ? 2 : 1);
-  if (last_x >= 0) HIPCHK(hipStreamWaitEvent(st, PE[S + 1 + last_x], 0));  // join the comm stream
+  if (c.timing) HIPCHK(hipEventRecord(c.ev.kr[2 * (size_t)S + 1], st));
+  c.nlaunch = bat.launches;
+  return 0;
+}
+
+// Level-synchronous shards, in order: every shard's level l, then its
+// exchange, all on the solve stream (the host-staged transport, blocks of
+// < 4 top values, GM_F_SHARD_INORDER)
+static int plane_levels_inorder(PlaneSolve& c) {
+  for (uint32_t l = 0; l <= c.S; l++) {
+    if (c.timing) HIPCHK(hipEventRecord(c.ev.kr[2 * l], c.st));
+    for (gm_solver* s : c.ss) plane_launch(s, l);
+    int rc = plane_exchange(c.ss, l, c.mode, c.st);
+    if (rc) return rc;
+    if (c.timing) HIPCHK(hipEventRecord(c.ev.kr[2 * l + 1], c.st));
+  }
+  c.nlaunch = (u64)c.S + 1;
+  return 0;
+}
+
+static bool plane_pipelined(const PlaneSolve& c) {
+  return (c.mode == 1 || c.mode == 2) && !c.staged && c.s0->pg.B >= 4 && !(c.s0->flags & GM_F_SHARD_INORDER);
+}
+// Level-synchronous shards (RCCL or in-process copies), pipelined: each
+// level's launch is split into the planes that read no halo plane -- the
+// boundary slices the exchange sends are among them when blocks hold >= 4
+// top values -- and the ones that do.  Own part -> event -> exchange on the
+// comm stream -> event; the boundary part of the NEXT level waits for it, so
+// the exchange of level l overlaps the boundary part of l and the own part
+// of l + 1.
+static int plane_levels_piped(PlaneSolve& c) {
+  gm_solver* s0 = c.s0;
+  hipStream_t st = c.st;
+  const uint32_t S = c.S;
+  if (!s0->cstream) HIPCHK(hipStreamCreateWithFlags(&s0->cstream, hipStreamNonBlocking));
+  while (s0->pev.size() < 2 * ((size_t)S + 1)) {
+    hipEvent_t e;
+    HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    s0->pev.push_back(e);
+  }
+  hipStream_t cs = s0->cstream;
+  hipEvent_t* PE = s0->pev.data();  // [0, S]: own part of level l done; [S+1, 2S+2): exchange of l done
+  for (uint32_t l = 0; l <= S; l++) {
+    if (c.timing) HIPCHK(hipEventRecord(c.ev.kr[2 * l], st));
+    for (gm_solver* s : c.ss) plane_launch(s, l, 1);
+    HIPCHK(hipEventRecord(PE[l], st));
+    HIPCHK(hipStreamWaitEvent(cs, PE[l], 0));
+    int rc = plane_exchange(c.ss, l, c.mode, cs);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(PE[S + 1 + l], cs));
+    // the boundary planes read the halos of levels l - 1 and l - 2
+    if (l >= 1) HIPCHK(hipStreamWaitEvent(st, PE[S + l], 0));
+    for (gm_solver* s : c.ss) plane_launch(s, l, 2);
+    if (c.timing) HIPCHK(hipEventRecord(c.ev.kr[2 * l + 1], st));
+  }
+  c.nlaunch = 2 * ((u64)S + 1);
+  HIPCHK(hipStreamWaitEvent(st, PE[2 * S + 1], 0));  // join the comm stream (its last exchange)
+  return 0;
+}
+
+// The end of every solve's enqueue: a failed launch of the backward, e2, the
+// finish kernels, and a queued solve's completion event.  GM_PARTIAL: the
+// solve stopped before its last step (waited for here).
+static int plane_solve_finish(PlaneSolve& c, gm_result* out) {
+  gm_solver* s0 = c.s0;
+  hipStream_t st = c.st;
   {
     const hipError_t e = hipGetLastError();  // (a failed launch of the backward)
     if (e != hipSuccess) {
-      if (!staged || mode == 2) return fail(GM_EHIP, "plane backward: %s", hipGetErrorString(e));
+      if (!c.staged || c.mode == 2) return fail(GM_EHIP, "plane backward: %s", hipGetErrorString(e));
       // staged shards: deferred, so the end-of-solve reduction is still entered
       if (!s0->defer_rc) staged_defer(s0, fail(GM_EHIP, "plane backward: %s", hipGetErrorString(e)), st);
     }
   }
-  if (join()) return GM_EHIP;
-  if (!lite) HIPCHK(hipEventRecord(e2, st));
-  if (overlap) HIPCHK(hipStreamWaitEvent(st, e1, 0));  // the counts and state resets before the finish
-  if (stop < 2 * T) {
+  int rc = plane_join(c);
+  if (rc) return rc;
+  if (!c.lite) HIPCHK(hipEventRecord(c.e2, st));
+  if (c.overlap) HIPCHK(hipStreamWaitEvent(st, c.e1, 0));  // the counts and state resets before the finish
+  if (c.stop < 2 * c.T) {
     HIPCHK(hipStreamSynchronize(st));
-    cleanup();
-    out->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    out->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c.t0).count();
     out->word_bits = 8 * s0->pwb;
     return GM_PARTIAL;
   }
-  for (gm_solver* s : ss)
+  for (gm_solver* s : c.ss)
     plane_form_dispatch(s, [&](auto WB, auto) {
-      if (flow)  // (the one-launch solve: its own count slots, the result straight to pinned memory)
+      if (c.flow)  // (the one-launch solve: its own count slots, the result straight to pinned memory)
         hipLaunchKernelGGL((k_plane_finish<decltype(WB)::value, true>), dim3(1), dim3(1024), 0, st, s->d, s->pg,
                            (const void*)s->ptab, s->pbits, s->st, (const BlockCount*)s->bcount, s->pflow_grid,
-                           flow_host);
+                           c.flow_host);
       else
         hipLaunchKernelGGL((k_plane_finish<decltype(WB)::value, false>), dim3(1), dim3(1024), 0, st, s->d, s->pg,
                            (const void*)s->ptab, s->pbits, s->st, (const BlockCount*)s->bcount, 0u, (u64*)nullptr);
     });
   HIPCHK(hipGetLastError());
-  if (async) {  // queued: the counts into the slot's pinned memory, then its completion event
+  if (c.async) {  // queued: the counts into the slot's pinned memory, then its completion event
     PlaneSlot& q = s0->pring[s0->pq_next % kPlaneRing];
     if (!q.host) HIPCHK(hipHostMalloc((void**)&q.host, 8 * sizeof(u64), hipHostMallocDefault));
     if (!q.ev[3]) HIPCHK(hipEventCreate(&q.ev[3]));
-    if (!flow) HIPCHK(hipMemcpyAsync(q.host, s0->st->red, 5 * sizeof(u64), hipMemcpyDeviceToHost, st));
+    if (!c.flow) HIPCHK(hipMemcpyAsync(q.host, s0->st->red, 5 * sizeof(u64), hipMemcpyDeviceToHost, st));
     HIPCHK(hipEventRecord(q.ev[3], st));
     s0->pq_next++;
-    cleanup();
-    return 0;
   }
+  return 0;
+}
+
+// A blocking solve's end: the shards' counts reduced (over RCCL, the host
+// transport, or this process's shards), the times, the result
+static int plane_solve_reduce(PlaneSolve& c, gm_result* out) {
+  gm_solver* s0 = c.s0;
+  hipStream_t st = c.st;
+  const int mode = c.mode;
   if (mode == 1) {
     RCCL_LIVE(s0);
     ncclGroupStart();
@@ -1906,12 +1897,12 @@ static int run_planes(std::vector<gm_solver*> ss, gm_result* out, bool async) {
       return fail(GM_EHIP, "RCCL allreduce: %s", ncclGetErrorString(r != ncclSuccess ? r : r2 != ncclSuccess ? r2 : r3));
   }
   u64 red[5] = {0, 0, 0, 0, 0};
-  for (gm_solver* s : ss) {
+  for (gm_solver* s : c.ss) {
     u64 r[5];
     // (into pinned host memory: a pageable destination is staged and waited
     // for inside the copy call)
     if (!s->phost) HIPCHK(hipHostMalloc((void**)&s->phost, 8 * sizeof(u64), hipHostMallocDefault));
-    if (!flow) HIPCHK(hipMemcpyAsync(s->phost, s->st->red, sizeof r, hipMemcpyDeviceToHost, st));
+    if (!c.flow) HIPCHK(hipMemcpyAsync(s->phost, s->st->red, sizeof r, hipMemcpyDeviceToHost, st));
     HIPCHK(mode == 0 ? plane_wait(st) : hipStreamSynchronize(st));
     memcpy(r, s->phost, sizeof r);
     if (mode == 3) {
@@ -1932,31 +1923,53 @@ static int run_planes(std::vector<gm_solver*> ss, gm_result* out, bool async) {
   }
   auto t1 = std::chrono::steady_clock::now();
   float f = 0, b = 0;
-  HIPCHK(hipEventElapsedTime(&f, etail, e1));  // the forward's own span (it starts at etail)
-  HIPCHK(hipEventElapsedTime(&b, overlap ? e0 : e1, e2));  // overlap: the backward starts at e0
+  HIPCHK(hipEventElapsedTime(&f, c.etail, c.e1));  // the forward's own span (it starts at etail)
+  HIPCHK(hipEventElapsedTime(&b, c.overlap ? c.e0 : c.e1, c.e2));  // overlap: the backward starts at e0
   out->ms_forward = f;
   out->ms_backward = b;
-  out->ms_total = std::chrono::duration<double, std::milli>(t1 - t0).count();
-  if (timing) {
+  out->ms_total = std::chrono::duration<double, std::milli>(t1 - c.t0).count();
+  if (c.timing) {
+    const uint32_t S = c.S;
     float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, kx[0], kx[1]));
+    HIPCHK(hipEventElapsedTime(&ms, c.ev.kx[0], c.ev.kx[1]));
     out->ms_expand_kernels = ms;
     out->n_expand_launches = 1;
     double sr = 0;
-    if (per_level) {
+    if (c.per_level()) {
       for (uint32_t l = 0; l <= S; l++) {
-        HIPCHK(hipEventElapsedTime(&ms, kr[2 * l], kr[2 * l + 1]));
+        HIPCHK(hipEventElapsedTime(&ms, c.ev.kr[2 * l], c.ev.kr[2 * l + 1]));
         sr += ms;
       }
     } else {
-      HIPCHK(hipEventElapsedTime(&ms, kr[0], kr[2 * (size_t)S + 1]));
+      HIPCHK(hipEventElapsedTime(&ms, c.ev.kr[0], c.ev.kr[2 * (size_t)S + 1]));
       sr = ms;
     }
     out->ms_resolve_kernels = sr;
-    out->n_resolve_launches = nlaunch;
+    out->n_resolve_launches = c.nlaunch;
   }
-  cleanup();
-  return plane_result(ss, red, out);
+  return plane_result(c.ss, red, out);
+}
+
+static int run_planes(std::vector<gm_solver*> ss, gm_result* out, bool async) {
+  PlaneSolve c{ss, ss[0], async};
+  int rc = plane_solve_begin(c);
+  if (rc) return rc;
+  c.t0 = std::chrono::steady_clock::now();
+  HIPCHK(hipEventRecord(c.e0, c.st));
+  if ((rc = plane_fork(c))) return rc;
+  if (!c.overlap) {  // (overlap: plane_levels_table enqueues it)
+    if (!c.lite) HIPCHK(hipEventRecord(c.etail, c.st));  // (the forward's start: ms_forward)
+    if ((rc = plane_forward(c))) return rc;
+  }
+  c.s0->pflow_last = c.flow;
+  if (c.flow) rc = plane_backward_flow(c);
+  else if (c.staged) rc = plane_backward_staged_solve(c);
+  else if (c.mode == 0) rc = plane_levels_table(c);
+  else if (plane_pipelined(c)) rc = plane_levels_piped(c);
+  else rc = plane_levels_inorder(c);
+  if (rc) return rc;
+  if ((rc = plane_solve_finish(c, out)) || async) return rc;
+  return plane_solve_reduce(c, out);
 }
 
 // A queued solve's result (gm_solver_collect): wait for its completion

@@ -919,28 +919,6 @@ static int rank_shape(const Desc* d, RankShape* rs) {
     }
     byl[s].push_back(c);
   }
-  // Block order inside a level.  A child block (hv + e_x) is read by up to C
-  // parent blocks, one per column; in ascending code order those are up to
-  // (H+1)^(C-1) codes apart, so a child block's lines are fetched again by
-  // parents far away in time.  GM_RK_ORDER=morton orders a level's blocks by
-  // the bit-interleaved height digits instead (neighbours along any column
-  // mostly close together) -- A/B
-  if (const char* e = lab_env("GM_RK_ORDER")) {
-    if (!strcmp(e, "morton")) {
-      auto key = [&](uint32_t c) {
-        uint32_t dig[kRankMaxCols] = {}, v = c;
-        for (uint32_t x = 0; x < g.C; x++) {
-          dig[x] = v % g.R;
-          v /= g.R;
-        }
-        u64 k = 0;
-        for (int b = 3; b >= 0; b--)
-          for (int x = (int)g.C - 1; x >= 0; x--) k = k * 2 + ((dig[x] >> b) & 1u);
-        return k;
-      };
-      for (auto& v : byl) std::sort(v.begin(), v.end(), [&](uint32_t a, uint32_t b) { return key(a) < key(b); });
-    }
-  }
   rs->base.assign(nhv, 0);
   rs->lvhv.clear();
   rs->lvph.clear();
@@ -1091,15 +1069,6 @@ static int rk_dbg() {
   }();
   return v;
 }
-// the bit-sliced board kernel (k_rk_boards_sl) where it applies; GM_RK_SLICED=0
-// keeps the per-board one (A/B runs)
-static bool rk_sliced() {
-  static const bool on = [] {
-    const char* e = lab_env("GM_RK_SLICED");
-    return !(e && atoi(e) == 0);
-  }();
-  return on;
-}
 
 static int rank_grid(const gm_solver* s, u64 nitems) {
   return (int)std::max<u64>(1, std::min<u64>((nitems + 255) / 256, (u64)std::min(s->grid * 2, kCountSlots)));
@@ -1122,7 +1091,7 @@ static void rank_forward_level(gm_solver* s, hipStream_t st, uint32_t L) {
       hipLaunchKernelGGL((k_rk_boards_sl<CC, HH>), dim3(rank_grid(s, nb / 32)), dim3(256), 0, st, g, L,
                          s->rlvstart[L] >> 3, s->rlvoff[L], nb / 32, nreal);
     };
-    const bool sliced = L >= 5 && rk_sliced();
+    const bool sliced = L >= 5;  // the bit-sliced board kernel (k_rk_boards_sl) where it applies
     if (g.C == 6 && g.H == 4) {
       if (sliced) boards_sl(std::integral_constant<int, 6 * 16 + 4>());
       else boards(std::integral_constant<int, 6 * 16 + 4>());

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Pipeline model of the staged PLANES deal from kernel
-traces of ONE-STREAM shard groups (tools/r05_session.sh stage: every key of
+traces of ONE-STREAM shard groups (a profiled staged group solve: every key of
 every shard alone on the GPU, so a launch's duration is what it costs on a
 GPU of its own).
 
