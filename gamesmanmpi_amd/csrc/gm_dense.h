@@ -1694,20 +1694,26 @@ __global__ void k_dense_root(DenseView v, const uint32_t* words, const u64* bits
   }
 }
 
+// word of a key this table owns (NO_WORD for unreachable / not owned);
+// shared by k_dense_query and the move kernels (gm_moves.h)
+__device__ __forceinline__ uint32_t dense_word(const Desc& d, const DenseView& v, const uint32_t* words,
+                                               const u64* bits, uint32_t wbits, u64 key) {
+  u64 slot, L, p;
+  uint32_t w = NO_WORD;
+  if (dense_slot_of(d, key, &slot)) {
+    slot_split(d, slot, &L, &p);
+    uint64_t q;
+    if (dense_local(v, p, &q) && reach_bit(bits, L * v.Wbl + q))
+      w = dense_word_at(words, L * v.Wl + q, wbits);
+  }
+  return w;
+}
+
 // word of each key this table owns (NO_WORD for unreachable / not owned)
 __global__ void k_dense_query(Desc d, DenseView v, const uint32_t* words, const u64* bits, const u64* keys, u64 n,
                               uint32_t* out, uint32_t wbits) {
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
-    u64 slot, L, p;
-    uint32_t w = NO_WORD;
-    if (dense_slot_of(d, keys[i], &slot)) {
-      slot_split(d, slot, &L, &p);
-      uint64_t q;
-      if (dense_local(v, p, &q) && reach_bit(bits, L * v.Wbl + q))
-        w = dense_word_at(words, L * v.Wl + q, wbits);
-    }
-    out[i] = w;
-  }
+  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x)
+    out[i] = dense_word(d, v, words, bits, wbits, keys[i]);
 }
 
 // every reachable owned position -> its key (order arbitrary); v sweeps the

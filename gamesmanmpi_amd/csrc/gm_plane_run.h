@@ -71,16 +71,23 @@ __device__ __forceinline__ bool plane_locate(const Desc& d, const PlaneGeom& g, 
   return true;
 }
 
+// word of `key` in this table's planes (NO_WORD if unreached or not held
+// here); shared by k_plane_query and the move kernels (gm_moves.h)
+template <int WB>
+__device__ __forceinline__ uint32_t plane_word(const Desc& d, const PlaneGeom& g, const void* tab,
+                                               const uint32_t* bits, u64 key) {
+  u64 P;
+  uint32_t h0, h1, e, w = NO_WORD;
+  if (plane_locate(d, g, key, &P, &h0, &h1, &e) && ((plane_row_bits(bits, g, P, h1) >> h0) & 1u))
+    w = plane_vr<WB>(tab, P, h0, h1, e);
+  return w;
+}
+
 template <int WB>
 __global__ void k_plane_query(Desc d, PlaneGeom g, const void* tab, const uint32_t* bits, const u64* keys, u64 n,
                               uint32_t* out) {
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
-    u64 P;
-    uint32_t h0, h1, e, w = NO_WORD;
-    if (plane_locate(d, g, keys[i], &P, &h0, &h1, &e) && ((plane_row_bits(bits, g, P, h1) >> h0) & 1u))
-      w = plane_vr<WB>(tab, P, h0, h1, e);
-    out[i] = w;
-  }
+  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x)
+    out[i] = plane_word<WB>(d, g, tab, bits, keys[i]);
 }
 
 // the end of a solve, one launch: the root's word (only the shard that owns

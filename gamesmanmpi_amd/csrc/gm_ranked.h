@@ -842,13 +842,29 @@ __global__ __launch_bounds__(1024) void k_rk_finish(RankGeom g, u64 root_slot, D
   fill_red_body(st, bc);
 }
 
+// word of `key` at its computed slot (NO_WORD if unreached); shared by
+// k_rk_query and the move kernels (gm_moves.h)
+__device__ __forceinline__ uint32_t rk_word(const RankGeom& g, u64 key) {
+  u64 s;
+  uint32_t L, w = NO_WORD;
+  if (rk_slot_of(g, key, &s, &L) && ((g.reach[s >> 5] >> (s & 31)) & 1u)) w = g.words[s];
+  return w;
+}
+
 __global__ void k_rk_query(Desc d, RankGeom g, const u64* keys, u64 n, uint32_t* out) {
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
-    u64 s;
-    uint32_t L, w = NO_WORD;
-    if (rk_slot_of(g, keys[i], &s, &L) && ((g.reach[s >> 5] >> (s & 31)) & 1u)) w = g.words[s];
-    out[i] = w;
-  }
+  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x)
+    out[i] = rk_word(g, keys[i]);
+}
+
+// key of reached slot s0 + bit of level L (lvstart / lvoff: k_rk_scan's lvt halves)
+__device__ __forceinline__ u64 rk_slot_key(const RankGeom& g, const u64* lvstart, const u64* lvoff, uint32_t L,
+                                           u64 slot) {
+  const u64 i = slot - lvstart[L];
+  const u64 blk = i >> (L + 3);
+  const uint32_t a = (uint32_t)((i >> L) & 7u), pat = (uint32_t)(i & ((1ull << L) - 1));
+  RankPos p;
+  rk_unpack(g, g.lvph[lvoff[L] + blk], p);
+  return rk_key(g, p, pat, L, rk_hands(L, (uint32_t)__builtin_popcount(pat), a));
 }
 
 // every reached slot of every level: its key (positions) or its fingerprint
@@ -869,13 +885,9 @@ __global__ __launch_bounds__(256) void k_rk_scan(Desc d, RankGeom g, const u64* 
     u64 k = 0;
     if (!CK) k = atomicAdd(count, (u64)__builtin_popcountll(m));
     for (; m; m &= m - 1, k++) {
-      const u64 i = s0 + (u64)__builtin_ctzll(m) - lvstart[L];
-      const u64 blk = i >> (L + 3);
-      const uint32_t a = (uint32_t)((i >> L) & 7u), pat = (uint32_t)(i & ((1ull << L) - 1));
-      RankPos p;
-      rk_unpack(g, g.lvph[lvoff[L] + blk], p);
-      const u64 key = rk_key(g, p, pat, L, rk_hands(L, (uint32_t)__builtin_popcount(pat), a));
-      if (CK) ck_add(d, key, g.words[lvstart[L] + i], v);
+      const u64 slot = s0 + (u64)__builtin_ctzll(m);
+      const u64 key = rk_slot_key(g, lvstart, lvoff, L, slot);
+      if (CK) ck_add(d, key, g.words[slot], v);
       else if (k < cap) keys[k] = key;
     }
   }

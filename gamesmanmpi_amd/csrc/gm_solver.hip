@@ -850,11 +850,16 @@ __global__ __launch_bounds__(256) void k_resolve(Desc d, gm_slot* tab, u64 mask,
   block_add(&st->prims, prims);
 }
 
+// word of `key` in the hash table (NO_WORD if absent); shared by k_query and
+// the move kernels (gm_moves.h)
+__device__ __forceinline__ uint32_t hashed_word(const Desc& d, const gm_slot* tab, u64 mask, u64 key) {
+  u64 h = table_find(tab, mask, any_canon(d, key));  // symmetry hooks: the orbit's representative
+  return h == ~0ull ? NO_WORD : tab[h].word;
+}
+
 __global__ void k_query(Desc d, const gm_slot* tab, u64 mask, const u64* keys, u64 n, uint32_t* words) {
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
-    u64 h = table_find(tab, mask, any_canon(d, keys[i]));  // symmetry hooks: the orbit's representative
-    words[i] = h == ~0ull ? NO_WORD : tab[h].word;
-  }
+  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x)
+    words[i] = hashed_word(d, tab, mask, keys[i]);
 }
 
 __global__ void k_root_word(const gm_slot* tab, u64 mask, u64 root, DevState* st) {
@@ -1043,6 +1048,7 @@ struct gm_solver {
   uint32_t step_first = 0, step_stop = 0;  // gm_solver_set_steps (one solve)
   uint32_t rk = RK_NONE, pk = PK_NONE;      // dense kernel families (dense_choose)
   bool launch_err = false;                  // a launch found no kernel of the table's word width
+  bool solved = false;  // the buffers hold a finished full solve (gm_solver_moves / _line / _audit need one)
   // whole-solve HIP graphs of a one-table dense solve (run_dense): the
   // forward and the backward launches, captured on the first full solve
   hipGraphExec_t gfwd = nullptr, gbwd = nullptr;
@@ -2345,6 +2351,7 @@ int gm_solver_solve_async(gm_solver* s, uint64_t* ticket) {
   if (s->pq_next - s->pq_done >= (u64)kPlaneRing)
     return fail(GM_EINVAL, "%d solves queued: collect one first", kPlaneRing);
   const u64 t = s->pq_next;
+  s->solved = false;
   gm_result scratch;
   memset(&scratch, 0, sizeof scratch);
   const int rc = run_planes({s}, &scratch, true);
@@ -2357,11 +2364,21 @@ int gm_solver_collect(gm_solver* s, uint64_t ticket, gm_result* out) {
   if (!s || !out) return fail(GM_EINVAL, "bad argument");
   memset(out, 0, sizeof *out);
   if (s->mode != GM_MODE_PLANES || s->world > 1) return fail(GM_EINVAL, "queued solves: one-table PLANES solvers only");
-  return plane_collect(s, ticket, out);
+  const int rc = plane_collect(s, ticket, out);
+  s->solved = rc == 0 && s->pq_done == s->pq_next;  // (no later solve is rewriting the table)
+  return rc;
 }
 
+static int solver_solve(gm_solver* s, gm_result* out);
 int gm_solver_solve(gm_solver* s, gm_result* out) {
   if (!s || !out) return fail(GM_EINVAL, "bad argument");
+  s->solved = false;
+  const int rc = solver_solve(s, out);
+  s->solved = rc == 0;  // (GM_PARTIAL: stopped early, the table is not finished)
+  return rc;
+}
+
+static int solver_solve(gm_solver* s, gm_result* out) {
   memset(out, 0, sizeof *out);
   if (s->mode == GM_MODE_DENSE) return solve_dense(s, out);
   if (s->mode == GM_MODE_PLANES) return run_planes({s}, out);
@@ -3797,10 +3814,40 @@ int gm_solve_group(gm_solver** shards, int n, gm_result* out) {
   std::vector<gm_solver*> ss(shards, shards + n);
   for (gm_solver* s : ss)
     if (!s) return fail(GM_EINVAL, "null shard");
-  if (ss[0]->mode == GM_MODE_PLANES) return run_planes(ss, out);
-  if (ss[0]->mode == GM_MODE_BUCKETED) return run_bucketed_shards(ss, out);
-  if (ss[0]->mode == GM_MODE_RANKED) return ss[0]->world > 1 ? run_ranked_shards(ss, out) : run_ranked(ss[0], out);
-  return run_dense(ss, out);
+  for (gm_solver* s : ss) s->solved = false;
+  int rc;
+  if (ss[0]->mode == GM_MODE_PLANES) rc = run_planes(ss, out);
+  else if (ss[0]->mode == GM_MODE_BUCKETED) rc = run_bucketed_shards(ss, out);
+  else if (ss[0]->mode == GM_MODE_RANKED) rc = ss[0]->world > 1 ? run_ranked_shards(ss, out) : run_ranked(ss[0], out);
+  else rc = run_dense(ss, out);
+  for (gm_solver* s : ss) s->solved = rc == 0;
+  return rc;
+}
+
+#include "gm_moves.h"
+
+int gm_solver_moves(gm_solver* s, const uint64_t* keys_dev, uint64_t n, uint64_t* children_dev, uint32_t* words_dev,
+                    uint8_t* nchild_dev, int8_t* best_dev) {
+  if (!s || (n && (!keys_dev || !children_dev || !words_dev || !nchild_dev || !best_dev)))
+    return fail(GM_EINVAL, "bad argument");
+  const int rc = moves_ready(s, "gm_solver_moves");
+  if (rc || !n) return rc;
+  return moves_run(s, keys_dev, n, children_dev, words_dev, nchild_dev, best_dev);
+}
+
+int gm_solver_line(gm_solver* s, uint64_t key, uint64_t* keys_dev, uint32_t* words_dev, uint64_t cap, uint64_t* n) {
+  if (!s || !n || (cap && (!keys_dev || !words_dev))) return fail(GM_EINVAL, "bad argument");
+  *n = 0;
+  const int rc = moves_ready(s, "gm_solver_line");
+  if (rc || !cap) return rc;
+  return line_run(s, key, keys_dev, words_dev, cap, n);
+}
+
+int gm_solver_audit(gm_solver* s, uint64_t* bad_keys_dev, uint64_t cap, uint64_t out[4]) {
+  if (!s || !out || (cap && !bad_keys_dev)) return fail(GM_EINVAL, "bad argument");
+  const int rc = moves_ready(s, "gm_solver_audit");
+  if (rc) return rc;
+  return audit_run(s, bad_keys_dev, cap, out);
 }
 
 int gm_solver_query(gm_solver* s, const uint64_t* keys_dev, uint64_t n, uint32_t* words_dev) {

@@ -14,6 +14,13 @@ literal evaluated against nothing but literals, e.g. 4 or '...'), or for the
 game's initial position when none is given.  Descriptor-solved tables are
 keyed by the packed u64 key (GameSpec.key_of); graph-solved tables (game
 files without a descriptor) by str(position).
+
+    python -m gamesmanmpi_amd.db DIR --game GAME_FILE --moves [POSITION ...]
+
+adds, under each position, one row per legal move (the module's gen_moves /
+do_move) with the child's value and remoteness from the table, the best move
+marked with `*` (best_index below; the rule of gm_solver_moves,
+include/gamesman.h).  Host only: no GPU is touched.
 """
 import argparse
 import ast
@@ -89,12 +96,52 @@ class SolutionDB:
         return self.lookup_key(key)
 
 
+def best_index(children):
+    """Index of the best move among `children`, a list of (value,
+    remoteness) in gen_moves order -- the rule of gm_solver_moves: a WIN
+    parent (some child is a LOSS) takes the first LOSS child of the smallest
+    remoteness; a TIE parent the first TIE child of the largest remoteness
+    among TIE children; a DRAW parent the first DRAW child; a LOSS parent
+    the first child of the largest remoteness.  None without children or
+    with a child the table does not hold."""
+    if not children or any(c is None for c in children):
+        return None
+    WIN, LOSS, TIE, DRAW = range(4)
+    vals = [v for v, _ in children]
+    if LOSS in vals:
+        cand = [(r, i) for i, (v, r) in enumerate(children) if v == LOSS]
+        return min(cand)[1]
+    for pv in (TIE, DRAW):
+        if pv in vals:
+            cand = [(-r if pv == TIE else 0, i) for i, (v, r) in enumerate(children) if v == pv]
+            return min(cand)[1]
+    return min((-r, i) for i, (v, r) in enumerate(children))[1]
+
+
+def position_moves(db, mod, pos, spec=None):
+    """[(move, child position, (value, remoteness) or None)] for every legal
+    move of a non-primitive position, in gen_moves order."""
+    from .solver_launcher import ensure_src_utils
+    utils = ensure_src_utils()  # the constants the module itself imports
+    if mod.primitive(pos) != utils.UNDECIDED:
+        return []
+    out = []
+    for mv in mod.gen_moves(pos):
+        child = mod.do_move(pos, mv)
+        out.append((mv, child, db.lookup(child, spec)))
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="gamesmanmpi_amd.db")
     ap.add_argument("statsdir")
     ap.add_argument("--game", required=True, help="the game file that was solved")
+    ap.add_argument("--moves", action="store_true",
+                    help="list every legal move of each position with the child's "
+                         "value and remoteness; `*` marks the best move")
     ap.add_argument("positions", nargs="*")
     args = ap.parse_intermixed_args(argv)
+    from . import _lib
     from .solver_launcher import ensure_src_utils, load_game
     ensure_src_utils()
     mod = load_game(args.game)
@@ -106,12 +153,23 @@ def main(argv=None):
     todo = [ast.literal_eval(p) for p in args.positions] or [mod.initial_position()]
     rc = 0
     for pos in todo:
-        r = db.lookup(pos, spec)
+        try:
+            r = db.lookup(pos, spec)
+        except _lib.GmError:  # no key: outside the game's state space
+            r = None
         if r is None:
             print("%s: not reachable" % (pos,))
             rc = 1
         else:
             print("%s: %s in %d moves" % (pos, NAMES[r[0]], r[1]))
+            if args.moves:
+                rows = position_moves(db, mod, pos, spec)
+                best = best_index([c for _, _, c in rows])
+                for i, (mv, child, c) in enumerate(rows):
+                    what = "not reachable" if c is None else "%s in %d moves" % (NAMES[c[0]], c[1])
+                    print("  %s -> %s: %s%s" % (mv, child, what, " *" if i == best else ""))
+                    if c is None:
+                        rc = 1
     return rc
 
 

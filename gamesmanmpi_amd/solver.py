@@ -322,6 +322,65 @@ class Solver:
         return {"checksum": "%016x" % v[0], "positions": v[1], "win": v[2],
                 "loss": v[3], "tie": v[4], "draw": v[5]}
 
+    # -- move analysis and the whole-table audit ----------------------------
+    def moves(self, keys):
+        """(children u64[n, GM_MAXCHILD], words u32[n, GM_MAXCHILD],
+        nchild u8[n], best i8[n]) of `keys` (gm_solver_moves): each key's
+        children in gen_moves() order with their words (GM_EMPTY_KEY /
+        GM_NO_WORD in unused slots) and the index of the best move; a
+        primitive or unreachable key has nchild 0 and best -1."""
+        torch = self.torch
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        n, m = len(keys), _lib.GM_MAXCHILD
+        if n == 0:
+            return (np.zeros((0, m), np.uint64), np.zeros((0, m), np.uint32),
+                    np.zeros(0, np.uint8), np.zeros(0, np.int8))
+        kd = torch.from_numpy(keys.view(np.int64)).to(self.device)
+        cd = torch.empty((n, m), dtype=torch.int64, device=self.device)
+        wd = torch.empty((n, m), dtype=torch.int32, device=self.device)
+        nd = torch.empty(n, dtype=torch.uint8, device=self.device)
+        bd = torch.empty(n, dtype=torch.int8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().gm_solver_moves(
+                self._h, kd.data_ptr(), n, cd.data_ptr(), wd.data_ptr(),
+                nd.data_ptr(), bd.data_ptr()))
+        return (cd.cpu().numpy().view(np.uint64), wd.cpu().numpy().view(np.uint32),
+                nd.cpu().numpy(), bd.cpu().numpy())
+
+    def best_line(self, key=None, cap=None):
+        """(keys u64, values u8, remoteness u32) of the optimal line from
+        `key` (default: the root) to a primitive position, one kernel launch
+        (gm_solver_line); at most `cap` entries (default: one per level)."""
+        torch = self.torch
+        if key is None:
+            key = self.spec.root_key
+        cap = int(self.plan.max_levels) + 1 if cap is None else int(cap)
+        kd = torch.empty(max(1, cap), dtype=torch.int64, device=self.device)
+        wd = torch.empty(max(1, cap), dtype=torch.int32, device=self.device)
+        n = ctypes.c_uint64()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().gm_solver_line(
+                self._h, int(key), kd.data_ptr(), wd.data_ptr(), cap,
+                ctypes.byref(n)))
+        w = wd[:n.value].cpu().numpy().view(np.uint32)
+        return (kd[:n.value].cpu().numpy().view(np.uint64),
+                (w & 3).astype(np.uint8), (w >> 2).astype(np.uint32))
+
+    def audit(self, max_bad=64):
+        """Re-derive every stored word from its children's stored words
+        through the query path (gm_solver_audit): dict with positions, edges,
+        mismatches and bad_keys (up to max_bad mismatching keys, u64)."""
+        torch = self.torch
+        max_bad = int(max_bad)
+        bad = torch.empty(max(1, max_bad), dtype=torch.int64, device=self.device)
+        out = np.zeros(4, np.uint64)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().gm_solver_audit(
+                self._h, bad.data_ptr(), max_bad, out.ctypes.data))
+        return {"positions": int(out[0]), "edges": int(out[1]),
+                "mismatches": int(out[2]),
+                "bad_keys": bad[:int(out[3])].cpu().numpy().view(np.uint64)}
+
     def dump(self):
         """(keys u64, value u8, remoteness u32) for every reachable
         position."""

@@ -106,7 +106,45 @@ def build_parser():
                         "(gamesmanmpi_amd.checkpoint); removed on completion")
     p.add_argument("--checkpoint-every", type=int, default=32, metavar="N",
                    help="levels (steps) between checkpoints")
+    p.add_argument("--audit", action="store_true",
+                   help="one-GPU descriptor solves: after the solve, re-derive every "
+                        "stored word from its children's words through the query path "
+                        "(Solver.audit), print the counts and exit 1 on a mismatch")
+    p.add_argument("--line", action="store_true",
+                   help="one-GPU descriptor solves: print the optimal line from the "
+                        "initial position, one `position: VALUE in r moves` row per ply")
     return p
+
+
+def check_analysis_args(args, world, descriptor=True):
+    """--audit / --line read one whole table through its device descriptor:
+    a multi-rank run's tables are shards, a graph solve has no descriptor."""
+    asked = [f for f in ("audit", "line") if getattr(args, f)]
+    if not asked:
+        return
+    flags = " / ".join("--" + f for f in asked)
+    if world > 1:
+        raise SystemExit("%s: one-GPU solves only (%d ranks: every rank's table is a shard)"
+                         % (flags, world))
+    if not descriptor or args.layout == "graph":
+        raise SystemExit("%s: the game file needs a device descriptor (graph solves are not covered)"
+                         % flags)
+
+
+def print_line(spec, solver):
+    """The optimal line from the initial position, in db.py's row format."""
+    from gamesmanmpi_amd.solver import NAMES
+    keys, val, rem = solver.best_line()
+    for k, v, r in zip(keys.tolist(), val.tolist(), rem.tolist()):
+        print("%s: %s in %d moves" % (spec.pos_of(k), NAMES[v], r), flush=True)
+
+
+def run_audit(solver):
+    """Prints the audit's counts; 1 if any stored word disagrees."""
+    a = solver.audit()
+    print("audit: %d positions, %d edges, %d mismatches"
+          % (a["positions"], a["edges"], a["mismatches"]), flush=True)
+    return 1 if a["mismatches"] else 0
 
 
 DENSE_STEMS = ("four_to_one", "sum_four_to_one")  # rank-indexable descriptors
@@ -215,6 +253,7 @@ def main(argv=None):
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
+    check_analysis_args(args, world)
     if args.debug:  # src/debug.py:10-18: logging to logs/proc<rank>
         os.makedirs("logs", exist_ok=True)
         logging.basicConfig(filename="logs/proc%d" % rank, level=logging.DEBUG)
@@ -234,6 +273,7 @@ def main(argv=None):
     except ValueError as e:  # no device descriptor for this file
         if args.layout not in ("auto", "graph"):
             raise
+        check_analysis_args(args, world, descriptor=False)
         logging.debug("%s: solving through the host-enumerated graph", e)
         return solve_generic(args, game, rank, world, local)
     if args.layout == "graph":
@@ -326,11 +366,16 @@ def main(argv=None):
                               "ranks": world}), flush=True)
     if args.statsdir:
         write_stats(args.statsdir, rank, spec, solver, result, world)
+    rc = 0
+    if args.line:
+        print_line(spec, solver)
+    if args.audit:
+        rc = run_audit(solver)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()
         dist.destroy_process_group()
-    return 0
+    return rc
 
 
 if __name__ == "__main__":

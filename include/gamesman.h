@@ -284,6 +284,45 @@ void gm_solver_destroy(gm_solver *s);
  * without dumping it (the reference's equivalent is reading every
  * resolved/remote shelve entry, src/cache_dict.py:44-60). */
 int gm_solver_checksum(gm_solver *s, uint64_t out[6]);
+/* Move analysis and the whole-table audit of a finished solve: the walk a
+ * reference user does by hand over the resolved / remote shelves
+ * (src/cache_dict.py:44-79) with GameState.expand (src/game_state.py:58-84).
+ * All three are synchronous on the solver's stream, read the table only, and
+ * serve one-GPU solvers of every layout that hold a finished FULL solve:
+ * GM_EINVAL for a shard (world > 1: its positions' children live on other
+ * ranks) and for a solver that has not solved, or stopped early.
+ *
+ * gm_solver_moves: for each of n keys, children_dev[i * GM_MAXCHILD + j] =
+ * child j in gen_moves() order (GM_EMPTY_KEY in unused slots; a symmetric
+ * solve gives orbit representatives), words_dev[same] = its word
+ * (GM_NO_WORD in unused slots), nchild_dev[i] = the count, best_dev[i] = the
+ * index of the best move, or -1 for a primitive or unreachable key (those
+ * have nchild 0).  The best move, by the value the children give the parent
+ * (_res_red / _remote_red, src/process.py):
+ *   WIN : the first LOSS child of the smallest remoteness
+ *   TIE : the first TIE child of the largest remoteness among TIE children
+ *         (the parent's own remoteness is max over ALL children + 1, as the
+ *         reference computes it, and may come from another child)
+ *   DRAW: the first DRAW child
+ *   LOSS: the first child of the largest remoteness */
+int gm_solver_moves(gm_solver *s, const uint64_t *keys_dev, uint64_t n,
+                    uint64_t *children_dev, uint32_t *words_dev,
+                    uint8_t *nchild_dev, int8_t *best_dev);
+/* The optimal line from `key`: (key, word) of the position, then of its best
+ * child, ... until a primitive position or `cap` entries; *n = entries
+ * written (0 for an unreachable key).  One kernel launch for the whole
+ * line. */
+int gm_solver_line(gm_solver *s, uint64_t key, uint64_t *keys_dev,
+                   uint32_t *words_dev, uint64_t cap, uint64_t *n);
+/* Re-derives every reachable position's word from its children's stored
+ * words (primitive(): remoteness 0; else the reduction of
+ * src/process.py:120-123 and _res_red / _remote_red) and compares it with
+ * the stored one, all through the query path of gm_solver_query -- not the
+ * kernels that wrote the table.  out[0] = positions, out[1] = edges (both
+ * equal gm_result's), out[2] = mismatches, out[3] = mismatching keys written
+ * to bad_keys_dev (the first `cap` found, in no order; cap may be 0). */
+int gm_solver_audit(gm_solver *s, uint64_t *bad_keys_dev, uint64_t cap,
+                    uint64_t out[4]);
 /* change GM_F_* flags of an existing solver (e.g. kernel timing) */
 int gm_solver_set_flags(gm_solver *s, uint32_t flags);
 /* Level-granular stop / resume (checkpoints; SURVEY.md §8f rank 2 -- the
