@@ -1,7 +1,7 @@
 // gm_bucketed_shard.h -- BUCKETED levels sharded by the reference's own
 // ownership rule, owner(pos) = md5(str(pos)) % P (GameState.get_hash,
 // src/game_state.py:22-30; used by src/process.py:157-160 to route every
-// LOOK_UP).  Included by gm_solver.hip after solve_bucketed.
+// LOOK_UP).  Included by gm_solver.hip after gm_bucketed_run.h.
 //
 // Every rank keeps the one-GPU BUCKETED structures (gm_bucketed.h) for the
 // positions it owns -- unique keys per level grouped by fine bucket, words,
@@ -389,18 +389,11 @@ static int run_bucketed_shards(std::vector<gm_solver*> ss, gm_result* out) {
     return hipSuccess;
   };
   auto t0 = std::chrono::steady_clock::now();
-  hipEvent_t e0, e1, e2;
-  HIPCHK(hipEventCreate(&e0));
-  HIPCHK(hipEventCreate(&e1));
-  HIPCHK(hipEventCreate(&e2));
-  auto done_events = [&]() {
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipEventDestroy(e2);
-  };
+  SolveEvents ev;
+  if (ev.begin()) return GM_EHIP;
+  const hipEvent_t e0 = ev.e0, e1 = ev.e1, e2 = ev.e2;
   auto bail = [&](int code) {
     (void)sync_all();
-    done_events();
     return code;
   };
   HIPCHK(hipEventRecord(e0, st));
@@ -1105,7 +1098,6 @@ static int run_bucketed_shards(std::vector<gm_solver*> ss, gm_result* out) {
   float fms = 0, bms = 0;
   HIPCHK(hipEventElapsedTime(&fms, e0, e1));
   HIPCHK(hipEventElapsedTime(&bms, e1, e2));
-  done_events();
   out->ms_forward = fms;
   out->ms_backward = bms;
   out->ms_total = std::chrono::duration<double, std::milli>(t1 - t0).count();

@@ -319,7 +319,7 @@ template <int MAXH>
 __global__ __launch_bounds__(256) void k_dense_pull_words(Desc d, DenseView v, u64* bits, u64 L, u64 root_p,
                                                           const u64* __restrict__ masks,
                                                           const uint32_t* __restrict__ glist, XcdShares xs) {
-  // mask tables (built once on the host at solver creation, gm_solver.hip
+  // mask tables (built once on the host at solver creation, gm_dense_run.h
   // build_mask_tables): M[0..63] = TS, M[64 (i + 1) + t] = TD[i][t]
   __shared__ u64 M[64 * (MAXH + 1)];
   // one thread per 64-prefix bitmap word of the band, or of the level's
@@ -1488,7 +1488,7 @@ __global__ __launch_bounds__(256, GM_R8C_MINB) void k_dense_resolve8c(Desc d, Ro
   if (Q.S == 0) block_add(&st->prims, (u64)Q.npos);  // one launch per solve
 }
 
-// Packed word halos (shards, gm_solver.hip exchange_words): the non-hole
+// Packed word halos (shards, gm_dense_run.h exchange_words): the non-hole
 // words of a halo slice at level L move between the table and a dense
 // buffer in COLUMN order -- live columns in colperm order (digit sum gs
 // ascending), slots ascending inside a column.  With x = S - t and y = x -

@@ -1957,7 +1957,7 @@ static int plane_solve_reduce(PlaneSolve& c, gm_result* out) {
   return plane_result(c.ss, red, out);
 }
 
-static int run_planes(std::vector<gm_solver*> ss, gm_result* out, bool async) {
+static int run_planes(std::vector<gm_solver*> ss, gm_result* out, bool async = false) {
   PlaneSolve c{ss, ss[0], async};
   int rc = plane_solve_begin(c);
   if (rc) return rc;

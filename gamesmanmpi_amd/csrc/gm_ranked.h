@@ -1173,8 +1173,10 @@ static int run_ranked(gm_solver* s, gm_result* out) {
     HIPCHK(hipMemcpy(&wb, &s->st->word_bits, sizeof wb, hipMemcpyDeviceToHost));
     if (wb != 0x208u) return fail(GM_EINVAL, "resume: the scratch holds no ranked solve");
   }
+  SolveEvents se;
   hipEvent_t ev[4];
-  for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+  for (auto& e : ev)
+    if (se.make(&e)) return GM_EHIP;
   auto t0 = std::chrono::steady_clock::now();
   HIPCHK(hipEventRecord(ev[0], st));
   if (first == 0) {
@@ -1196,7 +1198,6 @@ static int run_ranked(gm_solver* s, gm_result* out) {
   HIPCHK(hipEventRecord(ev[2], st));
   if (stop < 2 * T) {
     HIPCHK(hipStreamSynchronize(st));
-    for (auto& e : ev) (void)hipEventDestroy(e);
     out->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     out->word_bits = 8;
     return GM_PARTIAL;
@@ -1210,7 +1211,6 @@ static int run_ranked(gm_solver* s, gm_result* out) {
   float f = 0, b = 0;
   HIPCHK(hipEventElapsedTime(&f, ev[0], ev[1]));
   HIPCHK(hipEventElapsedTime(&b, ev[1], ev[2]));
-  for (auto& e : ev) (void)hipEventDestroy(e);
   out->ms_forward = f;
   out->ms_backward = b;
   out->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

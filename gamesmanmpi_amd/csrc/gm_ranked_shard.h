@@ -290,28 +290,13 @@ static int run_ranked_shards(std::vector<gm_solver*> ss, gm_result* out) {
   }
   const int mode = group ? 4 : s0->xfer ? 3 : 1;
   if (mode == 1 && !s0->comm) return fail(GM_EINVAL, "shard %d/%d has no communicator (gm_solver_comm_init)", s0->rank, W);
-  // the solve's events, destroyed on EVERY return (the HIPCHK early
-  // returns included: they used to skip cleanup() and leak them)
-  struct Events {
-    std::vector<hipEvent_t> v;
-    void clear() {
-      for (auto e : v) (void)hipEventDestroy(e);
-      v.clear();
-    }
-    ~Events() { clear(); }
-  } ev;
-  auto cleanup = [&]() { ev.clear(); };
-  auto new_event = [&](hipEvent_t* e, unsigned fl) -> int {
-    HIPCHK(hipEventCreateWithFlags(e, fl));
-    ev.v.push_back(*e);
-    return 0;
-  };
-  hipEvent_t e0, e1, e2;
-  if (new_event(&e0, 0) || new_event(&e1, 0) || new_event(&e2, 0)) return GM_EHIP;
+  SolveEvents ev;  // the solve's events, destroyed on every return
+  if (ev.begin()) return GM_EHIP;
+  const hipEvent_t e0 = ev.e0, e1 = ev.e1, e2 = ev.e2;
   std::vector<hipEvent_t> PE(ss.size()), CE(ss.size()), JE(ss.size());
   for (size_t i = 0; i < ss.size(); i++)
-    if (new_event(&PE[i], hipEventDisableTiming) || new_event(&CE[i], hipEventDisableTiming) ||
-        new_event(&JE[i], hipEventDisableTiming))
+    if (ev.make(&PE[i], hipEventDisableTiming) || ev.make(&CE[i], hipEventDisableTiming) ||
+        ev.make(&JE[i], hipEventDisableTiming))
       return GM_EHIP;
   hipStream_t st = s0->stream;
   auto t0 = std::chrono::steady_clock::now();
@@ -371,10 +356,7 @@ static int run_ranked_shards(std::vector<gm_solver*> ss, gm_result* out) {
       }
     } else if (mode == 1) {
       gm_solver* s = s0;
-      if (s->gabort && s->gabort->load(std::memory_order_acquire)) {
-        cleanup();
-        return fail(GM_EHIP, "RCCL group aborted: a peer shard failed (shard %d/%d)", s->rank, s->world);
-      }
+      RCCL_LIVE(s);
       ncclGroupStart();
       ncclResult_t r = ncclSuccess;
       for (int p = 0; p < W && r == ncclSuccess; p++) {
@@ -385,10 +367,8 @@ static int run_ranked_shards(std::vector<gm_solver*> ss, gm_result* out) {
           r = ncclRecv(s->rko_rb + rko_roff(s, L, s->rank, p), nr, ncclUint8, p, s->comm, s->stream);
       }
       const ncclResult_t r2 = ncclGroupEnd();
-      if (r != ncclSuccess || r2 != ncclSuccess) {
-        cleanup();
+      if (r != ncclSuccess || r2 != ncclSuccess)
         return fail(GM_EHIP, "RCCL level exchange: %s", ncclGetErrorString(r != ncclSuccess ? r : r2));
-      }
     } else {  // mode 3: pairwise rounds, send to rank + d, receive from rank - d
       gm_solver* s = s0;
       for (int dd = 1; dd < W; dd++) {
@@ -398,10 +378,7 @@ static int run_ranked_shards(std::vector<gm_solver*> ss, gm_result* out) {
         if (ns) o.push_back({s->rko_pk, ns});
         if (nr) in.push_back({s->rko_rb + rko_roff(s, L, s->rank, rp), nr});
         int rc = xfer_ranges(s, o, sp, in, rp, s->stream);
-        if (rc) {
-          cleanup();
-          return rc;
-        }
+        if (rc) return rc;
       }
     }
     for (gm_solver* s : ss) {
@@ -424,18 +401,13 @@ static int run_ranked_shards(std::vector<gm_solver*> ss, gm_result* out) {
   }
   HIPCHK(hipGetLastError());
   if (mode == 1) {
-    if (s0->gabort && s0->gabort->load(std::memory_order_acquire)) {
-      cleanup();
-      return fail(GM_EHIP, "RCCL group aborted: a peer shard failed (shard %d/%d)", s0->rank, s0->world);
-    }
+    RCCL_LIVE(s0);
     ncclGroupStart();
     ncclResult_t r = ncclAllReduce(s0->st->red, s0->st->red, 4, ncclUint64, ncclSum, s0->comm, st);
     ncclResult_t r2 = ncclAllGather(s0->st->red + 4, s0->errg, 1, ncclUint64, s0->comm, st);
     ncclResult_t r3 = ncclGroupEnd();
-    if (r != ncclSuccess || r2 != ncclSuccess || r3 != ncclSuccess) {
-      cleanup();
+    if (r != ncclSuccess || r2 != ncclSuccess || r3 != ncclSuccess)
       return fail(GM_EHIP, "RCCL allreduce: %s", ncclGetErrorString(r != ncclSuccess ? r : r2 != ncclSuccess ? r2 : r3));
-    }
   }
   for (size_t i = 0; i < ss.size(); i++)
     if (ss[i]->stream != st) {
@@ -451,10 +423,7 @@ static int run_ranked_shards(std::vector<gm_solver*> ss, gm_result* out) {
     if (mode == 3) {
       std::vector<u64> all((size_t)5 * W);
       int rc = xfer_call(s, GM_XFER_ALLGATHER, r, sizeof r, -1, all.data(), all.size() * 8, -1);
-      if (rc) {
-        cleanup();
-        return rc;
-      }
+      if (rc) return rc;
       for (int q = 0; q < W; q++)
         for (int i = 0; i < 5; i++) red[i] = (i == 4) ? (red[i] | all[(size_t)q * 5 + i]) : red[i] + all[(size_t)q * 5 + i];
       continue;
@@ -470,7 +439,6 @@ static int run_ranked_shards(std::vector<gm_solver*> ss, gm_result* out) {
   float f = 0, b = 0;
   HIPCHK(hipEventElapsedTime(&f, e0, e1));
   HIPCHK(hipEventElapsedTime(&b, e1, e2));
-  cleanup();
   out->ms_forward = f;
   out->ms_backward = b;
   out->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

@@ -1,24 +1,40 @@
 // gm_solver.hip -- tier-synchronous retrograde solver for gfx950 (MI355X)
-// behind the C-ABI of include/gamesman.h.
+// behind the C-ABI of include/gamesman.h.  The library is ONE translation
+// unit: this file holds what every layout shares and the C-ABI, and includes
+// the layouts' kernels and host paths in this order:
 //
-// Replaces the reference's asynchronous per-state job machinery
-// (src/process.py:37-267, src/job.py) with a level-synchronous pipeline:
+//   gm_codec.h gm_games.h gm_md5.h  keys, the games' moves, md5 owners
+//   gm_plane.h           PLANES kernels
+//   (here)               errors, SolveEvents, the game registry, the dense /
+//                        halo / group / column geometry, DevState, the HASHED
+//                        kernels (k_seed, k_expand, k_finalize, k_resolve, ...)
+//   gm_dense.h           DENSE kernels
+//   gm_keyed_shard.h     md5-sharded HASHED kernels (gm_ks_*)
+//   gm_bucketed.h        BUCKETED kernels
+//   (here)               checksum kernels, struct gm_solver, the HASHED host
+//                        path (run_hashed), the codec C-ABI, k_fill_red
+//   gm_dense_run.h       DENSE host path: setup, launches, halo exchanges,
+//                        run_dense (no kernels)
+//   gm_plane_run.h       PLANES host path and its late kernels
+//   gm_ranked.h gm_ranked_shard.h  RANKED kernels and host path, its md5 shards
+//   gm_bucketed_run.h    BUCKETED host path (no kernels)
+//   gm_bucketed_shard.h  md5-sharded BUCKETED levels
+//   (here)               the C-ABI over the layouts: plans, creation, solves
+//   gm_moves.h           move analysis and the table audit
+//   (here)               readers, gm_solve, gm_ks_*, the explicit-graph solve
 //
-//   forward, level L = 0..T-1   K1+K2  k_expand<G>: every position of level L
-//                                      is tested with primitive(); the
-//                                      non-primitive ones generate their
-//                                      children (gen_moves+do_move fused),
-//                                      which are inserted into the HBM hash
-//                                      table by 64-bit CAS; a child inserted
-//                                      for the first time is appended
-//                                      (wave-aggregated atomics) to the
-//                                      position store of level L+1 or L+2.
-//   backward, level L = T-1..0  K3     k_resolve<G>: each position of level L
-//                                      re-generates its children, probes
-//                                      their 32-bit words and reduces them
-//                                      with the reference-canonical rule of
-//                                      _res_red/_remote_red (SURVEY §8a
-//                                      A8/A9), then stores its own word.
+// The HASHED pipeline (this file) replaces the reference's asynchronous
+// per-state job machinery (src/process.py:37-267, src/job.py) with a
+// level-synchronous one:
+//   forward, level L = 0..T-1 (K1+K2, k_expand<G>): every position of level L
+//     is tested with primitive(); the non-primitive ones generate their
+//     children (gen_moves+do_move fused), which are inserted into the HBM hash
+//     table by 64-bit CAS; a child inserted for the first time is appended
+//     (wave-aggregated atomics) to the position store of level L+1 or L+2.
+//   backward, level L = T-1..0 (K3, k_resolve<G>): each position of level L
+//     re-generates its children, probes their 32-bit words and reduces them
+//     with the reference-canonical rule of _res_red/_remote_red (SURVEY §8a
+//     A8/A9), then stores its own word.
 //
 // HBM layout (caller-allocated, gamesman.h):
 //   table  : gm_slot[2^k] {u64 key, u32 word, u32 spare}, open addressing,
@@ -50,7 +66,6 @@
 #include <memory>
 #include <type_traits>
 #include <map>
-#include <mutex>
 #include <thread>
 #include <atomic>
 
@@ -98,6 +113,49 @@ static int fail(int code, const char* fmt, ...) {
     hipError_t e_ = (x);                                                            \
     if (e_ != hipSuccess) return fail(GM_EHIP, "%s: %s", #x, hipGetErrorString(e_)); \
   } while (0)
+
+// The events made for ONE solve, destroyed on every return path.  Events
+// that live with the solver (pev, pse, the ring slots') are not made here.
+struct SolveEvents {
+  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;  // start, forward end, backward end
+  std::vector<hipEvent_t> kx, kr;  // kernel timing: start / stop pairs of the forward's / backward's launches
+  SolveEvents() = default;
+  SolveEvents(const SolveEvents&) = delete;
+  SolveEvents& operator=(const SolveEvents&) = delete;
+  ~SolveEvents() {
+    for (hipEvent_t e : all) (void)hipEventDestroy(e);
+  }
+  int make(hipEvent_t* e, unsigned flags = 0) {
+    HIPCHK(hipEventCreateWithFlags(e, flags));
+    all.push_back(*e);
+    return 0;
+  }
+  // e0, e1, e2, then (pairs > 0) kx and kr of `pairs` start / stop pairs each
+  int begin(size_t pairs = 0) {
+    if (make(&e0) || make(&e1) || make(&e2)) return GM_EHIP;
+    kx.resize(2 * pairs);
+    kr.resize(2 * pairs);
+    for (auto& e : kx)
+      if (make(&e)) return GM_EHIP;
+    for (auto& e : kr)
+      if (make(&e)) return GM_EHIP;
+    return 0;
+  }
+  // milliseconds summed over the first n pairs of kx / kr
+  static int pairs_ms(const std::vector<hipEvent_t>& p, int n, double* sum) {
+    *sum = 0;
+    for (int i = 0; i < n; i++) {
+      float ms = 0;
+      HIPCHK(hipEventElapsedTime(&ms, p[2 * i], p[2 * i + 1]));
+      *sum += ms;
+    }
+    return 0;
+  }
+
+ private:
+  std::vector<hipEvent_t> all;
+};
+
 
 // queued one-table PLANES solves (gm_solver_solve_async): a ring slot holds
 // one solve's events (start, forward end, backward end, its completion --
@@ -335,7 +393,6 @@ static int dense_geom(const Desc* d, int rank, int world, DenseGeom* g) {
   v.p_hi = v.Wl;
   return 0;
 }
-static uint32_t dense_plan_bits(const Desc* d, int world, uint32_t flags);
 // word area of a dense table: 8- or 16-bit order forms when the plan chose
 // them (dense_plan_bits: one-GPU K_SUM tables the 16- / 8-prefix kernels
 // handle), else 32-bit
@@ -346,28 +403,6 @@ static u64 dense_bits_bytes(const Desc* d, const DenseGeom& g) {
   return (u64)d->max_levels * g.v.Wbl / 8;
 }
 
-struct gm_solver;
-struct PlaneShape;
-static bool plane_ok(const Desc* d, int world);
-static bool plane_wanted(const Desc* d, uint32_t flags, int world);
-static int plan_planes(const Desc* d, int rank, int world, uint32_t flags, uint64_t max_table_bytes, gm_plan_t* out,
-                       bool* fits);
-static int plane_setup(gm_solver* s, const gm_buffers* buf);
-static int run_planes(std::vector<gm_solver*> ss, gm_result* out, bool async = false);
-static int plane_collect(gm_solver* s, u64 ticket, gm_result* out);
-static int plane_query(gm_solver* s, const uint64_t* keys_dev, uint64_t n, uint32_t* words_dev);
-static int plane_positions(gm_solver* s, uint64_t* keys_dev, uint64_t cap, uint64_t* n);
-static void plane_checksum_launch(gm_solver* s, u64* acc);
-static bool rank_wanted(const Desc* d, uint32_t flags);
-static bool rank_ok(const Desc* d);
-static int plan_ranked(const Desc* d, uint64_t max_table_bytes, gm_plan_t* out, bool* fits);
-static int rank_setup(gm_solver* s, const gm_buffers* buf);
-static int plan_ranked_shard(const Desc* d, int world, uint64_t max_table_bytes, gm_plan_t* out);
-static int run_ranked_shards(std::vector<gm_solver*> ss, gm_result* out);
-static int run_ranked(gm_solver* s, gm_result* out);
-static int rank_query(gm_solver* s, const uint64_t* keys_dev, uint64_t n, uint32_t* words_dev);
-static int rank_positions(gm_solver* s, uint64_t* keys_dev, uint64_t cap, uint64_t* n);
-static int rank_scan(gm_solver* s, bool ck, u64* keys_dev, u64 cap, u64* acc);
 
 static const Desc* get_game(int id) {
   std::lock_guard<std::mutex> lk(g_mu);
@@ -1180,249 +1215,6 @@ static void do_resolve(gm_solver* s, int L) {
   }
 }
 
-// Blocks of 256 threads of `kernel` that fit on the device at once (a
-// multiple of 8, one share per XCD): list sweeps launch exactly that many,
-// since blocks that start late would sweep their grid-stride items out of
-// order.  Cached per kernel.
-static int resident_blocks(const void* kernel) {
-  static std::mutex mu;
-  static std::map<const void*, int> cache;
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find(kernel);
-  if (it != cache.end()) return it->second;
-  int per_cu = 0, dev = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, 0) != hipSuccess || per_cu < 1) per_cu = 2;
-  (void)hipGetDevice(&dev);
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-  const int r = std::max(8, (per_cu * cus) & ~7);
-  cache[kernel] = r;
-  return r;
-}
-
-// Column jobs of level L over a shard view's listed slices: each slice's
-// live columns are one range of the digit-sum-sorted permutation.  False
-// if no column is live.
-static bool build_col_jobs(const gm_solver* s, const DenseView& v, u64 L, ColJobs& J) {
-  J.n = 0;
-  J.cum[0] = 0;
-  const int64_t S = (int64_t)s->d.root_sum - (int64_t)L;
-  for (uint32_t i = 0; i < v.nsl; i++) {
-    const int64_t t = (int64_t)v.st[i];
-    const int64_t hi = std::min<int64_t>(S - t, s->cg.maxgs);
-    const int64_t lo = std::max<int64_t>(S - t - (int64_t)s->d.heap[0] - s->cg.mj, 0);
-    if (hi < lo) continue;
-    const uint32_t a = s->cstart[(size_t)lo], b = s->cstart[(size_t)hi + 1];
-    if (a == b) continue;
-    J.lo[J.n] = a;
-    J.u[J.n] = (uint32_t)v.sl[i];
-    J.t[J.n] = (uint32_t)t;
-    J.cum[J.n + 1] = J.cum[J.n] + (b - a);
-    J.n++;
-  }
-  return J.n > 0;
-}
-
-// Forward (pull): power-of-two tables run one thread per 64-prefix bitmap
-// word (k_dense_pull_words; world 1 over the level's live-group list), other
-// bases one prefix per lane (k_dense_pull).
-template <int MAXH, bool POW2>
-static void dense_launch_pull_t(gm_solver* s, const DenseView& v, int grid, u64 L, u64 root_p) {
-  if (POW2 && s->pk == PK_WORDS) {
-    const uint32_t* gl = nullptr;
-    u64 groups = (v.p_hi - v.p_lo + 63) / 64;
-    XcdShares xs{};
-    int g;
-    if (s->glist && !v.blk) {  // the level's live 256-prefix groups, one share per XCD
-      gl = s->glist + s->goff[L];
-      if (s->goff[L + 1] == s->goff[L]) return;
-      uint32_t widest = 0;
-      for (int x = 0; x < 9; x++) xs.o[x] = s->gxcd[(size_t)L * 9 + x];
-      for (int x = 0; x < 8; x++) widest = std::max(widest, xs.o[x + 1] - xs.o[x]);
-      const u64 per = ((u64)widest * 4 + kBlock - 1) / kBlock;  // blocks per XCD
-      g = (int)(kXcds * std::min<u64>(per, (u64)s->grid / kXcds));
-    } else {
-      g = (int)std::min<u64>((groups + kBlock - 1) / kBlock, (u64)s->grid);
-    }
-    hipLaunchKernelGGL((k_dense_pull_words<MAXH>), dim3(g), dim3(kBlock), 0, s->stream, s->d, v, s->bits, L,
-                       root_p, s->masks, gl, xs);
-    return;
-  }
-  hipLaunchKernelGGL((k_dense_pull<MAXH, POW2>), dim3(grid), dim3(kBlock), 0, s->stream, s->d, v, s->bits, L,
-                     root_p);
-}
-// Backward (resolve) by the family fixed at creation (s->rk, dense_choose).
-template <int MAXH, bool POW2>
-static void dense_launch_resolve_t(gm_solver* s, const DenseView& v, int grid, u64 L) {
-  if constexpr (POW2 && MAXH >= 2) {
-    if (s->rk != RK_SCALAR) {
-      const uint32_t* gl = nullptr;
-      u64 units = (v.p_hi - (v.p_lo & ~255ull) + 3) / 4;
-      if (s->glist && !v.blk) {  // live groups of level L, 64 units each
-        gl = s->glist + s->goff[L];
-        units = (s->goff[L + 1] - s->goff[L]) * 64;
-        if (!units) return;
-      }
-      const int resident = resident_blocks((const void*)k_dense_resolve4<MAXH, false>);
-      // shards: column jobs over the level's listed slices (a view that
-      // lists no slices -- too many to list -- takes the band sweep)
-      if constexpr (MAXH >= 3) {
-        if (v.blk && s->colperm && v.nsl > 0 && v.nsl <= (uint32_t)kMaxColJobs) {
-          ColJobs J;
-          if (!build_col_jobs(s, v, L, J)) return;
-          const RowGeom rg{v.Wl, v.Wbl, v.Z};
-          if (s->w16) {  // 16-bit shard table: octets, two columns per wave
-            const u64 cu8 = (u64)((J.cum[J.n] + 1) / 2) * 64;
-            const int g8 = (int)std::min<u64>(
-                std::min<u64>(((cu8 + kBlock - 1) / kBlock + 7) & ~7ull,
-                              (u64)resident_blocks((const void*)k_dense_resolve8c<MAXH>)),
-                (u64)kCountSlots);
-            hipLaunchKernelGGL((k_dense_resolve8c<MAXH>), dim3(g8), dim3(kBlock), 0, s->stream, s->d, rg,
-                               (uint16_t*)s->words, s->bits, L, s->st, s->colperm, J, s->bcount);
-            return;
-          }
-          const u64 cu = (u64)J.cum[J.n] * 64;
-          const int gc = (int)std::min<u64>(((cu + kBlock - 1) / kBlock + 7) & ~7ull,
-                                            (u64)resident_blocks((const void*)k_dense_resolve4c<MAXH>));
-          hipLaunchKernelGGL((k_dense_resolve4c<MAXH>), dim3(gc), dim3(kBlock), 0, s->stream, s->d, rg, s->words,
-                             s->bits, L, s->st, s->colperm, J);
-          return;
-        }
-      }
-      if (s->w8) {  // 8-bit table: sixteen prefixes per lane over the live-group list (world 1)
-        if (!gl) {
-          s->launch_err = true;
-          return;
-        }
-        XcdShares xs;
-        for (int x = 0; x < 9; x++) xs.o[x] = s->gxcd[(size_t)L * 9 + x];
-        for (int x = 1; x < 8; x++) xs.o[x] &= ~3u;  // shares start at entries divisible by 4: a wave = four groups
-        const u64 u16 = (u64)xs.o[8] * 16;
-        const int rp = resident_blocks((const void*)k_dense_resolve16p<MAXH>);
-        const int gp = (int)std::min<u64>(std::min<u64>(((u16 + kBlock - 1) / kBlock + 7) & ~7ull, (u64)rp),
-                                          (u64)kCountSlots);
-        hipLaunchKernelGGL((k_dense_resolve16p<MAXH>), dim3(gp), dim3(kBlock), 0, s->stream, s->d, v,
-                           (uint8_t*)s->words, s->bits, L, s->st, gl, xs, s->bcount);
-        return;
-      }
-      if (s->w16) {
-        // 16-bit table: octets over the live-group list (world 1).  A 16-bit
-        // shard table always lists its slices (dense_choose), so reaching
-        // here without a list is a bug: flag it instead of running a kernel
-        // of the wrong word width.
-        if (!gl) {
-          s->launch_err = true;
-          return;
-        }
-        XcdShares xs;
-        for (int x = 0; x < 9; x++) xs.o[x] = s->gxcd[(size_t)L * 9 + x];
-        for (int x = 1; x < 8; x++) xs.o[x] &= ~1u;  // shares start at even entries: a wave = two whole groups
-        const u64 u8 = (u64)xs.o[8] * 32;
-        const int rp = resident_blocks((const void*)k_dense_resolve8p<MAXH>);
-        const int gp = (int)std::min<u64>(std::min<u64>(((u8 + kBlock - 1) / kBlock + 7) & ~7ull, (u64)rp),
-                                          (u64)kCountSlots);
-        hipLaunchKernelGGL((k_dense_resolve8p<MAXH>), dim3(gp), dim3(kBlock), 0, s->stream, s->d, v,
-                           (uint16_t*)s->words, s->bits, L, s->st, gl, xs, s->bcount);
-        return;
-      }
-      const int g = (int)std::min<u64>(((units + kBlock - 1) / kBlock + 7) & ~7ull, (u64)resident);
-      if (gl) {  // 32-bit words over the list, software-pipelined
-        XcdShares xs;
-        for (int x = 0; x < 9; x++) xs.o[x] = s->gxcd[(size_t)L * 9 + x];
-        const int rp = resident_blocks((const void*)k_dense_resolve4p<MAXH>);
-        const int gp = (int)std::min<u64>(((units + kBlock - 1) / kBlock + 7) & ~7ull, (u64)rp);
-        hipLaunchKernelGGL((k_dense_resolve4p<MAXH>), dim3(gp), dim3(kBlock), 0, s->stream, s->d, v, s->words,
-                           s->bits, L, s->st, gl, xs);
-      } else if (v.blk)
-        hipLaunchKernelGGL((k_dense_resolve4<MAXH, true>), dim3(g), dim3(kBlock), 0, s->stream, s->d, v, s->words,
-                           s->bits, L, s->st, nullptr, XcdShares{});
-      else
-        hipLaunchKernelGGL((k_dense_resolve4<MAXH, false>), dim3(g), dim3(kBlock), 0, s->stream, s->d, v, s->words,
-                           s->bits, L, s->st, nullptr, XcdShares{});
-      return;
-    }
-  }
-  if (s->w16 || s->w8) {  // never chosen with the one-prefix kernel (dense_choose)
-    s->launch_err = true;
-    return;
-  }
-  if (v.blk)
-    hipLaunchKernelGGL((k_dense_resolve<MAXH, POW2, true, 1, true>), dim3(grid), dim3(kBlock), 0, s->stream, s->d,
-                       v, s->words, s->bits, L, s->st);
-  else if (v.Wl * 4 <= 0xFFFFFFF0ull)
-    hipLaunchKernelGGL((k_dense_resolve<MAXH, POW2, true, 1, false>), dim3(grid), dim3(kBlock), 0, s->stream, s->d,
-                       v, s->words, s->bits, L, s->st);
-  else
-    hipLaunchKernelGGL((k_dense_resolve<MAXH, POW2, false, 1, false>), dim3(grid), dim3(kBlock), 0, s->stream, s->d,
-                       v, s->words, s->bits, L, s->st);
-}
-// kernels are instantiated per exact heap count 1..8 (16 = generic)
-template <bool POW2>
-static void dense_launch_pull_p(gm_solver* s, const DenseView& v, int grid, u64 L, u64 root_p) {
-  switch (s->d.nheaps) {
-    case 1: dense_launch_pull_t<1, POW2>(s, v, grid, L, root_p); break;
-    case 2: dense_launch_pull_t<2, POW2>(s, v, grid, L, root_p); break;
-    case 3: dense_launch_pull_t<3, POW2>(s, v, grid, L, root_p); break;
-    case 4: dense_launch_pull_t<4, POW2>(s, v, grid, L, root_p); break;
-    case 5: dense_launch_pull_t<5, POW2>(s, v, grid, L, root_p); break;
-    case 6: dense_launch_pull_t<6, POW2>(s, v, grid, L, root_p); break;
-    case 7: dense_launch_pull_t<7, POW2>(s, v, grid, L, root_p); break;
-    case 8: dense_launch_pull_t<8, POW2>(s, v, grid, L, root_p); break;
-    default: dense_launch_pull_t<16, POW2>(s, v, grid, L, root_p); break;
-  }
-}
-template <bool POW2>
-static void dense_launch_resolve_p(gm_solver* s, const DenseView& v, int grid, u64 L) {
-  switch (s->d.nheaps) {
-    case 1: dense_launch_resolve_t<1, POW2>(s, v, grid, L); break;
-    case 2: dense_launch_resolve_t<2, POW2>(s, v, grid, L); break;
-    case 3: dense_launch_resolve_t<3, POW2>(s, v, grid, L); break;
-    case 4: dense_launch_resolve_t<4, POW2>(s, v, grid, L); break;
-    case 5: dense_launch_resolve_t<5, POW2>(s, v, grid, L); break;
-    case 6: dense_launch_resolve_t<6, POW2>(s, v, grid, L); break;
-    case 7: dense_launch_resolve_t<7, POW2>(s, v, grid, L); break;
-    case 8: dense_launch_resolve_t<8, POW2>(s, v, grid, L); break;
-    default: dense_launch_resolve_t<16, POW2>(s, v, grid, L); break;
-  }
-}
-static void dense_launch_pull(gm_solver* s, const DenseView& v, int grid, u64 L, u64 root_p) {
-  if (s->d.pow2) dense_launch_pull_p<true>(s, v, grid, L, root_p);
-  else dense_launch_pull_p<false>(s, v, grid, L, root_p);
-}
-static void dense_launch_resolve(gm_solver* s, const DenseView& v, int grid, u64 L) {
-  if (s->d.pow2) dense_launch_resolve_p<true>(s, v, grid, L);
-  else dense_launch_resolve_p<false>(s, v, grid, L);
-}
-
-// Tail runs (world 1, lists; gm_dense.h k_dense_pull_tail /
-// k_dense_resolve16_tail): one workgroup walks the run's levels
-template <int MAXH>
-static void dense_launch_tail_t(gm_solver* s, const TailRun& R, bool pull, u64 root_p) {
-  if (pull) {
-    hipLaunchKernelGGL((k_dense_pull_tail<MAXH>), dim3(1), dim3(kTailThreads), 0, s->stream, s->d, s->view, s->bits,
-                       root_p, s->masks, s->glist, R);
-    return;
-  }
-  if constexpr (MAXH >= 2)
-    hipLaunchKernelGGL((k_dense_resolve16_tail<MAXH>), dim3(1), dim3(kTailThreads), 0, s->stream, s->d, s->view,
-                       (uint8_t*)s->words, s->bits, s->st, s->glist, R, s->bcount);
-  else
-    s->launch_err = true;
-}
-static void dense_launch_tail(gm_solver* s, const TailRun& R, bool pull, u64 root_p) {
-  if (!R.n) return;
-  switch (s->d.nheaps) {
-    case 1: dense_launch_tail_t<1>(s, R, pull, root_p); break;
-    case 2: dense_launch_tail_t<2>(s, R, pull, root_p); break;
-    case 3: dense_launch_tail_t<3>(s, R, pull, root_p); break;
-    case 4: dense_launch_tail_t<4>(s, R, pull, root_p); break;
-    case 5: dense_launch_tail_t<5>(s, R, pull, root_p); break;
-    case 6: dense_launch_tail_t<6>(s, R, pull, root_p); break;
-    case 7: dense_launch_tail_t<7>(s, R, pull, root_p); break;
-    case 8: dense_launch_tail_t<8>(s, R, pull, root_p); break;
-    default: dense_launch_tail_t<16>(s, R, pull, root_p); break;
-  }
-}
-
 static std::string err_text(uint32_t e) {
   std::string s;
   if (e & ERR_TABLE_FULL) s += " table-full";
@@ -1438,6 +1230,89 @@ static std::string err_text(uint32_t e) {
   if (e & ERR_PLANE_STALL) s += " plane-flow-stalled";
   return s;
 }
+
+// HASHED solve of one keyed table (the pipeline of the file header)
+static int run_hashed(gm_solver* s, gm_result* out) {
+  const int T = s->d.max_levels;
+  // steps [first, stop) of the 2T (gm_solver_set_steps); forward level L is
+  // step L (level T-1 expands nothing), backward level L is step 2T-1-L
+  const int first = (int)s->step_first, stop = s->step_stop ? (int)s->step_stop : 2 * T;
+  s->step_first = s->step_stop = 0;
+  const bool timing = (s->flags & GM_F_KERNEL_TIMING) && first == 0 && stop == 2 * T;
+  SolveEvents ev;  // kx / kr: per-launch start/stop pairs
+  if (ev.begin(timing ? (size_t)T : 0)) return GM_EHIP;
+  auto t0 = std::chrono::steady_clock::now();
+  HIPCHK(hipEventRecord(ev.e0, s->stream));
+  if (first == 0) {
+    // fresh table: keys EMPTY, words NO_WORD
+    HIPCHK(hipMemsetAsync(s->tab, 0xFF, (s->mask + 1) * sizeof(gm_slot), s->stream));
+    HIPCHK(hipMemsetAsync(s->st, 0, devstate_bytes(T), s->stream));
+    hipLaunchKernelGGL(k_seed, dim3(1), dim3(64), 0, s->stream, s->tab, s->mask, s->lv, s->st, s->d.root);
+  }
+  for (int L = std::max(first, 0); L + 1 < T && L < stop; L++) {
+    if (timing) HIPCHK(hipEventRecord(ev.kx[2 * L], s->stream));
+    do_expand(s, L);
+    if (timing) HIPCHK(hipEventRecord(ev.kx[2 * L + 1], s->stream));
+    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, s->stream, s->st, L, s->lcap);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(ev.e1, s->stream));
+  for (int L = T - 1; L >= 0; L--) {
+    const int k = 2 * T - 1 - L;
+    if (k < first) continue;
+    if (k >= stop) break;
+    if (timing) HIPCHK(hipEventRecord(ev.kr[2 * L], s->stream));
+    do_resolve(s, L);
+    if (timing) HIPCHK(hipEventRecord(ev.kr[2 * L + 1], s->stream));
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(ev.e2, s->stream));
+  if (stop < 2 * T) {  // stopped early: the state stays on the device for a resume
+    HIPCHK(hipStreamSynchronize(s->stream));
+    out->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return GM_PARTIAL;
+  }
+  hipLaunchKernelGGL(k_root_word, dim3(1), dim3(64), 0, s->stream, s->tab, s->mask, s->d.root, s->st);
+  HIPCHK(hipGetLastError());
+  std::vector<unsigned char> host(devstate_bytes(T));
+  HIPCHK(hipMemcpyAsync(host.data(), s->st, host.size(), hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  auto t1 = std::chrono::steady_clock::now();
+  const DevState* hs = (const DevState*)host.data();
+  const uint32_t word = hs->root_word;
+  float f = 0, b = 0;
+  HIPCHK(hipEventElapsedTime(&f, ev.e0, ev.e1));
+  HIPCHK(hipEventElapsedTime(&b, ev.e1, ev.e2));
+  out->ms_forward = f;
+  out->ms_backward = b;
+  out->ms_total = std::chrono::duration<double, std::milli>(t1 - t0).count();
+  if (timing) {
+    if (SolveEvents::pairs_ms(ev.kx, T - 1, &out->ms_expand_kernels)) return GM_EHIP;
+    if (SolveEvents::pairs_ms(ev.kr, T, &out->ms_resolve_kernels)) return GM_EHIP;
+    out->n_expand_launches = (uint64_t)(T - 1);
+    out->n_resolve_launches = (uint64_t)T;
+  }
+  out->positions = hs->cursor_front + hs->cursor_back;
+  out->edges = hs->edges;
+  out->primitives = hs->prims;
+  out->max_level_width = (uint32_t)std::max<u64>(hs->max_width, 1);
+  uint32_t lv = 0;
+  for (int L = 0; L < T; L++) {
+    const LevelSeg& g = hs->seg[L];
+    if ((g.fe - g.fb) + (g.c2hi - g.c2lo) > 0) lv++;
+  }
+  out->levels = lv;
+  out->root_word = word;
+  if (hs->err) {
+    bool full = hs->err & (ERR_TABLE_FULL | ERR_LEVELS_FULL);
+    return fail(full ? GM_EFULL : GM_ECORRUPT, "solve failed:%s", err_text(hs->err).c_str());
+  }
+  if (word == NO_WORD) return fail(GM_ECORRUPT, "root unresolved");
+  out->root_value = (int32_t)(word & 3u);
+  out->root_remoteness = word >> 2;
+  return 0;
+}
+
 
 // ---------------------------------------------------------------------------
 // C-ABI
@@ -1644,20 +1519,6 @@ int gm_owner_host(int game, const uint64_t* keys, size_t n, int world_size, uint
   return 0;
 }
 
-static int plan_dense(const Desc* d, int rank, int world, uint32_t flags, uint64_t max_table_bytes, gm_plan_t* out,
-                      bool* fits) {
-  DenseGeom g;
-  int rc = dense_geom(d, rank, world, &g);
-  if (rc) return rc;
-  const u64 bytes = dense_words_bytes(d, g, dense_plan_bits(d, world, flags)) + dense_bits_bytes(d, g);
-  *fits = max_table_bytes == 0 || bytes <= max_table_bytes;
-  out->mode = GM_MODE_DENSE;
-  out->table_slots = (u64)d->max_levels * g.v.Wl;
-  out->table_bytes = bytes;
-  out->level_capacity = 1;
-  return 0;
-}
-
 int gm_shard_info(int game, int rank, int world, uint64_t out[8]) {
   const Desc* d = get_game(game);
   if (!d || !out) return fail(GM_EINVAL, "bad argument");
@@ -1667,6 +1528,94 @@ int gm_shard_info(int game, int rank, int world, uint64_t out[8]) {
   if (rc) return rc;
   const uint64_t v[8] = {g.v.B, g.nblocks, g.nb, (uint64_t)rank, g.v.Z, g.v.E, g.v.Wl, (uint64_t)world};
   memcpy(out, v, sizeof v);
+  return 0;
+}
+
+// the per-block counts summed into the table's totals and the solve's
+// reduction words (one block of 1024 threads; also the tail of the PLANES
+// finish kernel, k_plane_finish)
+__device__ __forceinline__ void fill_red_body(DevState* st, const BlockCount* bc) {
+  __shared__ u64 rn[16], re[16];
+  u64 sn = 0, se = 0;
+  for (int i = (int)threadIdx.x; i < kCountSlots; i += (int)blockDim.x) {
+    sn += bc[i].npos;
+    se += bc[i].edges;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    sn += __shfl_xor(sn, o);
+    se += __shfl_xor(se, o);
+  }
+  if (__lane_id() == 0) {
+    rn[threadIdx.x >> 6] = sn;
+    re[threadIdx.x >> 6] = se;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    sn = se = 0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); w++) {
+      sn += rn[w];
+      se += re[w];
+    }
+    st->cursor_front += sn;  // this table's totals (gm_solver_positions reads them)
+    st->edges += se;
+    st->red[0] = st->cursor_front;
+    st->red[1] = st->edges;
+    st->red[2] = st->prims;
+    st->red[3] = st->root_word == NO_WORD ? 0 : (u64)st->root_word + 1;
+    st->red[4] = st->err;
+  }
+}
+__global__ __launch_bounds__(1024) void k_fill_red(DevState* st, const BlockCount* bc) { fill_red_body(st, bc); }
+
+// the layouts' host paths (and the kernels that need DevState / gm_solver)
+#include "gm_dense_run.h"
+#include "gm_plane_run.h"
+#include "gm_ranked.h"
+#include "gm_ranked_shard.h"
+#include "gm_bucketed_run.h"
+#include "gm_bucketed_shard.h"
+
+int gm_rk_shard_stats(gm_solver* s, uint64_t out[2]) {
+  if (!s || !out) return fail(GM_EINVAL, "bad argument");
+  if (s->mode != GM_MODE_RANKED || s->world < 2 || !s->rko_own) return fail(GM_EINVAL, "not a ranked md5 shard");
+  HIPCHK(hipStreamSynchronize(s->stream));
+  HIPCHK(hipMemcpy(&out[0], &s->st->ks_cursor, sizeof(u64), hipMemcpyDeviceToHost));
+  out[1] = 0;
+  for (size_t L = 0; L < s->rko_tot_h.size() / (size_t)s->world; L++) out[1] += s->rko_tot_h[L * s->world + s->rank];
+  return 0;
+}
+
+int gm_plane_halo_plan(int game, int rank, int world, uint32_t flags, uint64_t* out, uint32_t levels) {
+  const Desc* d = get_game(game);
+  if (!d || !out || world < 2 || rank < 0 || rank >= world) return fail(GM_EINVAL, "bad argument");
+  if (!plane_ok(d, world)) return fail(GM_EINVAL, "game has no planes layout");
+  PlaneShape ps;
+  int rc = plane_shape(d, rank, world, flags, &ps);
+  if (rc) return rc;
+  const uint32_t steps = ps.stage_k ? ps.nrows : ps.S + 1;
+  if (levels < steps) return fail(GM_EINVAL, "out holds %u steps, the plan has %u", levels, steps);
+  memset(out, 0, (size_t)levels * world * 2 * sizeof(uint64_t));
+  std::unique_ptr<gm_solver> s(new gm_solver());
+  s->world = world;
+  s->rank = rank;
+  std::vector<uint8_t> lb;
+  rc = plane_lists(s.get(), ps, lb);
+  if (rc) return rc;
+  if (ps.stage_k) {  // staged: step = halo row, to rank + 1 / from rank - 1
+    for (uint32_t r = 0; r < ps.nrows; r++) {
+      if (rank + 1 < world) out[((size_t)r * world + rank + 1) * 2] = s->psnd_off[r + 1] - s->psnd_off[r];
+      if (rank > 0) out[((size_t)r * world + rank - 1) * 2 + 1] = s->prcv_off[r + 1] - s->prcv_off[r];
+    }
+    return 0;
+  }
+  for (uint32_t l = 0; l <= ps.S; l++)
+    for (int p = 0; p < world; p++) {
+      u64 n;
+      plane_seg(s->psnd_off, l, world, p, &n);
+      out[((size_t)l * world + p) * 2] = n;
+      plane_seg(s->prcv_off, l, world, p, &n);
+      out[((size_t)l * world + p) * 2 + 1] = n;
+    }
   return 0;
 }
 
@@ -1694,78 +1643,6 @@ int gm_plan_shard(int game, int rank, int world, uint32_t flags, uint64_t max_ta
   if (rc) return rc;
   if (!fits) return fail(GM_EFULL, "dense shard needs %llu bytes", (unsigned long long)out->table_bytes);
   return 0;
-}
-
-// ---- BUCKETED plan ---------------------------------------------------------
-// keyed games whose every move advances one level (the tier is the number
-// of pieces placed): the bucketed pipeline applies (gm_bucketed.h)
-// every move advances one level, and remoteness < 256 (packed backward answers)
-static bool bk_ok(const Desc* d) {
-  return (d->kind == K_TTT || d->kind == K_TOOT || d->kind == K_OTHELLO) && d->max_levels <= 256;
-}
-// edges bound for a positions bound: the known counts where the board and
-// bound match (SURVEY Appendix B / tests/golden), else a branching factor
-// above every known board's
-struct BkKnown {
-  int kind, L, H;
-  u64 P, E;
-};
-static const BkKnown* bk_known(const Desc* d) {
-  static const BkKnown kn[] = {
-      {K_TOOT, 3, 3, 11097ull, 27774ull},          {K_TOOT, 4, 3, 200127ull, 640648ull},
-      {K_TOOT, 4, 4, 3468773ull, 9932808ull},      {K_TOOT, 5, 4, 70184763ull, 226547754ull},
-      {K_TOOT, 6, 4, 1187212827ull, 4243234712ull}, {K_OTHELLO, 4, 4, 54089ull, 69916ull},
-      {K_TTT, 0, 0, 5478ull, 16167ull}};
-  for (const BkKnown& k : kn)
-    if (k.kind == d->kind && (d->kind == K_TTT || (k.L == d->L && k.H == d->H))) return &k;
-  return nullptr;
-}
-static u64 bk_edges_bound(const Desc* d, u64 P) {
-  const BkKnown* k = bk_known(d);
-  if (k && P <= k->P) return k->E + 1024;
-  const double ratio = d->kind == K_TOOT ? 3.6 : d->kind == K_TTT ? 3.0 : 2.0;
-  return (u64)(ratio * (double)P) + 1024;
-}
-// out-edges of the P positions an md5 shard owns: the md5 partition spreads
-// positions evenly and regardless of their move counts, so a shard's share of
-// the edges is its share of the positions -- the board's known edge / position
-// ratio (+2 %), else the per-kind ratio; not the whole board's edges, which
-// sized every shard of toot 6x4 for the full 4.2e9 (4 shards: out of memory)
-static u64 bk_shard_edges_bound(const Desc* d, u64 P) {
-  const BkKnown* k = bk_known(d);
-  if (k && P < k->P) return std::min<u64>(k->E, (u64)((double)k->E / (double)k->P * (double)P * 1.02)) + 1024;
-  return bk_edges_bound(d, P);
-}
-// in-edges of the widest level: a quarter of all edges (every known board
-// is below a fifth; a level over it returns GM_EFULL and the host re-plans)
-// (+5% and a run per partition: the count-free expand provisions each of the
-// 256 coarse partitions a 1/256 share of it, k_bk_expand<OVER>)
-static u64 bk_emax_bound(u64 E) { return std::min<u64>(E, std::max<u64>(E / 4, 1u << 20)) / 20 * 21 + (u64)kBkC * 4096; }
-struct BkScratch {
-  size_t lv, pbase, bh, ph, boff, tot, cbase, ah, cur, ucnt, total, gc, meta, end;
-};
-static BkScratch bk_scratch(int T) {
-  auto r = [](size_t b) { return (b + 255) / 256 * 256; };
-  BkScratch x;
-  size_t o = r(devstate_bytes(T));
-  x.lv = o; o += r(sizeof(BkLevel) * (size_t)T);
-  x.pbase = o; o += r((size_t)T * (kBkC + 1) * 4);
-  x.bh = o; o += r((size_t)kBkExpandBlocks * kBkC * 4);
-  x.ph = o; o += r((size_t)kBkExpandBlocks * kBkC * 4);
-  x.boff = o; o += r((size_t)kBkExpandBlocks * kBkC * 4);
-  x.tot = o; o += r(2 * kBkC * 4);
-  x.cbase = o; o += r((kBkC + 1) * 4);
-  const size_t NBmax = (size_t)kBkC << kBkMaxFineBits;
-  x.ah = o; o += r((size_t)T * kBkC * kBkC * 4);  // per level: answers per (child partition, parent range)
-  x.cur = o; o += r((kBkC + ((size_t)1 << (29 - kBkRangeBits)) + 1) * 4);  // B3 / B4 run cursors
-  x.ucnt = o; o += r(NBmax * 4);
-  x.total = o; o += r(2 * 8);
-  x.gc = o; o += r((2 * kBkC + 4) * 4);  // k_bk_expand<OVER>: partition cursors, parent-range totals, overflow flag
-  const size_t NRmax = (size_t)1 << (29 - kBkRangeBits);
-  // per level: cst, fo, rfo (twice: md5 shards' local-dedup form keeps a second cst / fo per level)
-  x.meta = o; o += r((size_t)T * 2 * (2 * (NBmax + 1) + NRmax + 1) * 4);
-  x.end = o;
-  return x;
 }
 
 int gm_plan(int game, uint64_t positions, uint32_t flags, uint64_t max_table_bytes, gm_plan_t* out) {
@@ -1862,97 +1739,6 @@ int gm_plan_keyed_shard(int game, int rank, int world, uint64_t positions, uint3
   return 0;
 }
 
-// Per-lane condition masks of a 64-prefix group for power-of-two layouts
-// (k_dense_pull_words): with j the lane's offset in the group,
-//   M[t]              = { j : sum_i digit_i(j) <= t }   (TS)
-//   M[64 (i + 1) + t] = { j : digit_i(j) <= t }         (TD[i], i >= 1)
-// They depend only on the descriptor, so they are built once here.
-static void build_mask_tables(const Desc& d, u64* M) {
-  memset(M, 0, kMaskTableWords * sizeof(u64));
-  for (int j = 0; j < 64; j++) {
-    uint32_t dj[16] = {0}, sj = 0;
-    for (int i = 1; i < d.nheaps; i++) {
-      dj[i] = (uint32_t)((j >> d.pshift[i]) & (d.base[i] - 1));
-      sj += dj[i];
-    }
-    for (int t = 0; t < 64; t++) {
-      if (sj <= (uint32_t)t) M[t] |= 1ull << j;
-      for (int i = 1; i < d.nheaps; i++)
-        if (dj[i] <= (uint32_t)t) M[64 * (i + 1) + t] |= 1ull << j;
-    }
-  }
-}
-
-// Column tables of the packed halos (k_halo_cols).  Slot j of a column
-// (j < 256, digit sum ds(j) over the digits below the top) is a non-hole of
-// slice x iff ds(j) in [y - heap0, y], y = x - gs: NY[y] counts them,
-// PB[x][g] sums NY over the columns of smaller sum, and tot[x] = PB[x][NG-1]
-// is the slice's non-hole total.
-static void build_halo_cols(const Desc& d, const HaloGeom& h, const std::vector<uint32_t>& cstart,
-                            std::vector<uint32_t>& PB, std::vector<uint32_t>& NY, std::vector<uint32_t>& CS,
-                            std::vector<uint32_t>& tot) {
-  const int H0 = (int)d.heap[0];
-  NY.assign((size_t)h.NYn, 0);
-  for (int j = 0; j < 256; j++) {
-    int ds = 0;
-    for (int i = 1; i < h.top; i++) ds += (int)(((uint32_t)j >> d.pshift[i]) & (d.base[i] - 1));
-    for (int y = ds; y <= ds + H0 && y < h.NYn; y++) NY[(size_t)y]++;
-  }
-  CS.assign((size_t)h.NG, 0);
-  std::vector<uint32_t> cnt((size_t)h.NG, 0);
-  for (int g = 0; g < h.NG; g++) {
-    CS[(size_t)g] = g + 1 < (int)cstart.size() ? cstart[(size_t)g] : cstart.back();
-    if (g + 1 < (int)cstart.size()) cnt[(size_t)g] = cstart[(size_t)g + 1] - cstart[(size_t)g];
-  }
-  PB.assign((size_t)h.XN * h.NG, 0);
-  tot.assign((size_t)h.XN, 0);
-  for (int x = 0; x < h.XN; x++) {
-    uint32_t run = 0;
-    for (int g = 0; g < h.NG; g++) {
-      PB[(size_t)x * h.NG + g] = run;
-      const int y = x - g;
-      if (y >= 0 && y < h.NYn) run += cnt[(size_t)g] * NY[(size_t)y];
-    }
-    tot[(size_t)x] = run;
-  }
-}
-
-static u64 blk_count(const gm_solver* s);
-// Kernel families of a dense solver (DenseResolveKind / DensePullKind),
-// chosen once from the descriptor, the geometry, the scratch the caller
-// provided and the flags.  16-bit tables: world 1 needs the live-group
-// lists (octets sweep only listed groups); shards need the column
-// permutation, packed 16-bit halos and every level's slices in one job list.
-static int dense_choose(gm_solver* s) {
-  const Desc& d = s->d;
-  const DenseView& v = s->view;
-  s->pk = d.pow2 ? PK_WORDS : PK_LANE;
-  const bool scalar = (s->flags & GM_F_RESOLVE_SCALAR) != 0;
-  const bool quad = d.pow2 && d.nheaps >= 2 && d.base[1] >= 4 && v.Wl * 4 <= 0xFFFFFFF0ull && (!v.blk || v.Z % 256 == 0);
-  const bool base16 = d.pow2 && d.kind == K_SUM && d.nheaps >= 2 && d.nheaps <= 8 && d.base[1] >= 8 &&
-                      d.root_sum < 0x7FFF && v.Wl * 2 <= 0xFFFFFFF0ull &&
-                      !(s->flags & (GM_F_WORDS32 | GM_F_RESOLVE_SCALAR));
-  s->w8 = false;
-  if (!v.blk) {
-    if (s->plan_bits < 32) {
-      if (!s->glist)
-        return fail(GM_EINVAL, "%u-bit dense table without live-group lists: scratch smaller than gm_plan's",
-                    s->plan_bits);
-      s->w16 = s->plan_bits == 16;
-      s->w8 = s->plan_bits == 8;
-      s->rk = s->w8 ? RK_HEX_LIST : RK_OCT_LIST;
-      return 0;
-    }
-    s->w16 = false;
-    s->rk = (scalar || !quad) ? RK_SCALAR : s->glist ? RK_QUAD_LIST : RK_QUAD_BAND;
-    return 0;
-  }
-  s->w16 = base16 && d.nheaps >= 3 && s->colperm && s->hg.on && s->halo16 && v.Z % 256 == 0 && v.E <= 0xFFFF &&
-           blk_count(s) * (v.B + 4) <= (u64)kMaxColJobs;
-  s->rk = s->w16 ? RK_OCT_COLS : (scalar || !quad) ? RK_SCALAR : s->colperm ? RK_QUAD_COLS : RK_QUAD_BAND;
-  return 0;
-}
-
 int gm_solver_create_shard(int game, int rank, int world, const gm_buffers* buf, gm_solver** out) {
   const Desc* d = get_game(game);
   if (!d || !buf || !out) return fail(GM_EINVAL, "bad argument");
@@ -2033,186 +1819,22 @@ int gm_solver_create_shard(int game, int rank, int world, const gm_buffers* buf,
     }
     s->own_stream = true;
   }
-  if (s->mode == GM_MODE_DENSE && d->pow2) {
-    std::vector<u64> m(kMaskTableWords);
-    build_mask_tables(*d, m.data());
-    hipError_t e = hipMemcpy((void*)s->masks, m.data(), m.size() * sizeof(u64), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      gm_solver_destroy(s);
-      return fail(GM_EHIP, "mask tables: %s", hipGetErrorString(e));
-    }
-    const ColGeom cg = col_geom(d);
-    std::vector<uint32_t> perm;
-    if (cg.on) build_colperm(d, cg, perm, s->cstart);
-    s->hg = halo_geom(d, world, (u64)(s->view.blk ? s->view.Wl / ((s->view.B + 4) * s->view.Z) : 1));
-    size_t off = scratch_bytes_for(d->max_levels);
-    const size_t hbytes = s->hg.on ? halo_bytes(s->hg) : 0;
-    // scratch: [halo tables + buffers | column permutation | group lists]
-    if (cg.on && buf->scratch_bytes >= off + hbytes + col_bytes(d)) {
-      uint32_t* dp = (uint32_t*)((char*)buf->scratch + off + hbytes);
-      e = hipMemcpy(dp, perm.data(), perm.size() * 4, hipMemcpyHostToDevice);
-      if (e != hipSuccess) {
-        gm_solver_destroy(s);
-        return fail(GM_EHIP, "column permutation: %s", hipGetErrorString(e));
-      }
-      s->colperm = dp;
-      s->cg = cg;
-    }
-    if (s->hg.on && s->colperm) {
-      char* base = (char*)buf->scratch + off;
-      auto r = [](size_t b) { return (b + 255) / 256 * 256; };
-      std::vector<uint32_t> PB, NY, CS;
-      build_halo_cols(*d, s->hg, s->cstart, PB, NY, CS, s->halo_tot);
-      uint32_t* pb = (uint32_t*)base;
-      uint32_t* ny = (uint32_t*)(base + r(PB.size() * 4));
-      uint32_t* cs = (uint32_t*)(base + r(PB.size() * 4) + r(NY.size() * 4));
-      e = hipMemcpy(pb, PB.data(), PB.size() * 4, hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMemcpy(ny, NY.data(), NY.size() * 4, hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMemcpy(cs, CS.data(), CS.size() * 4, hipMemcpyHostToDevice);
-      if (e != hipSuccess) {
-        gm_solver_destroy(s);
-        return fail(GM_EHIP, "halo tables: %s", hipGetErrorString(e));
-      }
-      s->ht = HaloTabs{pb, ny, cs, s->hg.NG, s->hg.NYn, s->hg.top};
-      s->halo_send = (uint32_t*)(base + halo_tab_bytes(s->hg));
-      s->halo_recv = s->halo_send + s->hg.nb * 2 * s->hg.Z;
-      s->halo16 = d->kind == K_SUM && d->root_sum < 32768;
-    } else {
-      s->hg.on = false;  // scratch from an older plan: whole-slice halos
-    }
-    off += hbytes + (s->colperm ? col_bytes(d) : 0);
-    const GroupGeom gg = group_geom(d, world);
-    const size_t gbytes = gg.on ? (group_entries(d, gg) * 4 + 255) / 256 * 256 : 0;
-    if (gg.on && !s->view.blk && buf->scratch_bytes >= off + gbytes) {
-      std::vector<uint16_t> gsum;
-      group_sums(d, gg, gsum);
-      std::vector<uint32_t> list;
-      list.reserve(gbytes / 4);
-      s->goff.assign((size_t)d->max_levels + 1, 0);
-      s->gxcd.assign((size_t)d->max_levels * 9, 0);
-      const int top = d->nheaps - 1;
-      const u64 C = d->pstride[top] / 256;  // groups per top-digit slice
-      bool cols = top >= 2 && d->pstride[top] % 256 == 0 && C >= 8;
-      const u64 tile = 0;  // columns per top-major tile (0: the XCD's whole range; tiles measured no gain)
-      const u64 NT = cols ? gg.groups / C : 1, NC = cols ? C : gg.groups;
-      std::vector<u64> live(NC);
-      for (int L = 0; L < d->max_levels; L++) {
-        s->goff[L] = list.size();
-        u64 tot = 0;
-        for (u64 c = 0; c < NC; c++) {
-          u64 n = 0;
-          for (u64 t = 0; t < NT; t++) n += group_live(d, gg, gsum[c + t * NC], L);
-          live[c] = n;
-          tot += n;
-        }
-        // 8 contiguous column ranges of ~equal live count, each walked
-        // top-major in tiles of `tile` columns
-        u64 c0 = 0, acc = 0;
-        for (int x = 0; x < 8; x++) {
-          s->gxcd[(size_t)L * 9 + x] = (uint32_t)(list.size() - s->goff[L]);
-          u64 c1 = c0;
-          const u64 want = tot * (u64)(x + 1) / 8;
-          while (c1 < NC && (acc < want || x == 7)) acc += live[c1++];
-          const u64 tw = tile ? tile : std::max<u64>(1, c1 - c0);
-          for (u64 ta = c0; ta < c1; ta += tw)
-            for (u64 t = 0; t < NT; t++)
-              for (u64 c = ta; c < std::min(c1, ta + tw); c++)
-                if (group_live(d, gg, gsum[c + t * NC], L)) list.push_back((uint32_t)(c + t * NC));
-          c0 = c1;
-        }
-        s->gxcd[(size_t)L * 9 + 8] = (uint32_t)(list.size() - s->goff[L]);
-      }
-      s->goff[d->max_levels] = list.size();
-      uint32_t* dl = (uint32_t*)((char*)buf->scratch + off);
-      e = list.empty() ? hipSuccess : hipMemcpy(dl, list.data(), list.size() * 4, hipMemcpyHostToDevice);
-      if (e != hipSuccess) {
-        gm_solver_destroy(s);
-        return fail(GM_EHIP, "group lists: %s", hipGetErrorString(e));
-      }
-      s->glist = dl;
-    }
+  int rc = 0;
+  switch (s->mode) {
+    case GM_MODE_DENSE: rc = dense_setup(s, buf); break;
+    case GM_MODE_BUCKETED: bk_setup(s, buf); break;
+    case GM_MODE_PLANES: rc = plane_setup(s, buf); break;
+    case GM_MODE_RANKED: rc = rank_setup(s, buf); break;
+    default: break;  // HASHED: the common fields are all of it
   }
-  if (s->mode == GM_MODE_BUCKETED) {
-    char* t = (char*)buf->table;
-    s->Pcap = buf->level_capacity;
-    s->Ecap = buf->table_slots;
-    // a shard of a world > 1 job also holds the md5 exchange buffers (24 B per staged record)
-    // (world > 1 also: the local-dedup form's in-edges, another 6 B per edge)
-    s->Emax = std::min<u64>((buf->table_bytes - 4 * s->Pcap - (world > 1 ? 12 : 6) * s->Ecap) / (world > 1 ? 48 : 24),
-                            0xFFFFFFF0ull);
-    s->bkK = (u64*)buf->levels;
-    s->bkW = (uint32_t*)t;
-    t += (4 * s->Pcap + 7) & ~7ull;
-    s->REp = (uint32_t*)t;
-    t += 4 * s->Ecap;
-    s->REc = (uint16_t*)t;
-    t += (2 * s->Ecap + 7) & ~7ull;
-    if (world > 1) {
-      s->REpl = (uint32_t*)t;
-      t += 4 * s->Ecap;
-      s->REcl = (uint16_t*)t;
-      t += (2 * s->Ecap + 7) & ~7ull;
-    }
-    // staging: [S1k | S1p | S1f] (the count-free expand writes the first 13
-    // Emax bytes of it in its chunked layout, BkChunked) then S2k
-    s->S1k = (u64*)t;
-    t += 8 * s->Emax;
-    s->S1p = (uint32_t*)t;
-    t += 4 * s->Emax;
-    s->S1f = (uint8_t*)t;  // (4 Emax bytes of the plan; one is used)
-    t += 4 * s->Emax;
-    s->S2k = (u64*)t;
-    t += 8 * s->Emax;
-    if (world > 1) {  // md5 exchange: records sent / received (keys, refs; answers reuse the key arrays)
-      s->XSk = (u64*)t;
-      t += 8 * s->Emax;
-      s->XSr = (uint32_t*)t;
-      t += 4 * s->Emax;
-      s->XRk = (u64*)t;
-      t += 8 * s->Emax;
-      s->XRr = (uint32_t*)t;
-    }
-    const BkScratch x = bk_scratch(d->max_levels);
-    char* sc = (char*)buf->scratch;
-    s->bkL = (BkLevel*)(sc + x.lv);
-    s->pbase = (uint32_t*)(sc + x.pbase);
-    s->bh = (uint32_t*)(sc + x.bh);
-    s->ph = (uint32_t*)(sc + x.ph);
-    s->boff = (uint32_t*)(sc + x.boff);
-    s->tot = (uint32_t*)(sc + x.tot);
-    s->cbase = (uint32_t*)(sc + x.cbase);
-    s->bkcur = (uint32_t*)(sc + x.cur);
-    s->bkah = (uint32_t*)(sc + x.ah);
-    s->bkgc = (uint32_t*)(sc + x.gc);
-    s->ucnt = (uint32_t*)(sc + x.ucnt);
-    s->bktotal = (u64*)(sc + x.total);
-    s->meta = (uint32_t*)(sc + x.meta);
-    s->meta_cap = (x.end - x.meta) / 4;
-  }
-  if (s->mode == GM_MODE_DENSE) {
-    int rc = dense_choose(s);
-    if (rc) {
-      gm_solver_destroy(s);
-      return rc;
-    }
-  }
-  if (s->mode == GM_MODE_PLANES) {
-    int rc = plane_setup(s, buf);
-    if (rc) {
-      gm_solver_destroy(s);
-      return rc;
-    }
-  }
-  if (s->mode == GM_MODE_RANKED) {
-    int rc = rank_setup(s, buf);
-    if (rc) {
-      gm_solver_destroy(s);
-      return rc;
-    }
+  if (rc) {  // (fail()'s message stands: gm_solver_destroy sets none)
+    gm_solver_destroy(s);
+    return rc;
   }
   *out = s;
   return 0;
 }
+
 
 int gm_solver_create(int game, const gm_buffers* buf, gm_solver** out) {
   return gm_solver_create_shard(game, 0, 1, buf, out);
@@ -2238,37 +1860,6 @@ int gm_solver_comm_init(gm_solver* s, const void* id) {
   s->comm = c;
   if (!s->errg && hipMalloc((void**)&s->errg, (size_t)s->world * sizeof(u64)) != hipSuccess)
     return fail(GM_EHIP, "error-mask gather buffer");
-  return 0;
-}
-
-static void halo_sigs(const gm_solver* s, u64 L, u64 out[4]);
-// host half of a dense shard's halo geometry, as gm_solver_create_shard
-// builds it from a gm_plan_shard scratch (column permutation present)
-static int shard_host_geom(const Desc* d, int rank, int world, gm_solver* s) {
-  DenseGeom g;
-  memset(&g, 0, sizeof g);
-  int rc = dense_geom(d, rank, world, &g);
-  if (rc) return rc;
-  s->d = *d;
-  s->mode = GM_MODE_DENSE;
-  s->view = g.v;
-  s->rank = rank;
-  s->world = world;
-  s->nblocks = g.nblocks;
-  s->hg.on = false;
-  if (d->pow2) {
-    const ColGeom cg = col_geom(d);
-    std::vector<uint32_t> perm;
-    if (cg.on) build_colperm(d, cg, perm, s->cstart);
-    s->hg = halo_geom(d, world, (u64)(s->view.blk ? s->view.Wl / ((s->view.B + 4) * s->view.Z) : 1));
-    if (s->hg.on && cg.on) {
-      std::vector<uint32_t> PB, NY, CS;
-      build_halo_cols(*d, s->hg, s->cstart, PB, NY, CS, s->halo_tot);
-      s->halo16 = d->kind == K_SUM && d->root_sum < 32768;
-    } else {
-      s->hg.on = false;
-    }
-  }
   return 0;
 }
 
@@ -2338,10 +1929,6 @@ void gm_solver_destroy(gm_solver* s) {
   delete s;
 }
 
-static int solve_dense(gm_solver* s, gm_result* out);
-static int solve_bucketed(gm_solver* s, gm_result* out);
-static int run_bucketed_shards(std::vector<gm_solver*> ss, gm_result* out);
-
 // Queued one-table PLANES solves: enqueue without waiting, collect later
 // (in order).  Solves queued back to back run back to back on the solver's
 // stream with no host round trip between them.
@@ -2369,1444 +1956,25 @@ int gm_solver_collect(gm_solver* s, uint64_t ticket, gm_result* out) {
   return rc;
 }
 
-static int solver_solve(gm_solver* s, gm_result* out);
+// the solve of one solver, or of the shards of an in-process group, by layout
+static int solve_by_mode(const std::vector<gm_solver*>& ss, gm_result* out) {
+  gm_solver* s = ss[0];
+  if (s->mode == GM_MODE_DENSE) return run_dense(ss, out);
+  if (s->mode == GM_MODE_PLANES) return run_planes(ss, out);
+  if (s->mode == GM_MODE_RANKED) return s->world > 1 ? run_ranked_shards(ss, out) : run_ranked(s, out);
+  if (s->mode == GM_MODE_BUCKETED) return s->world > 1 ? run_bucketed_shards(ss, out) : solve_bucketed(s, out);
+  if (s->world > 1) return fail(GM_EINVAL, "keyed-table shard %d/%d: drive it with gm_ks_* (md5 exchange)", s->rank, s->world);
+  return run_hashed(s, out);
+}
+
 int gm_solver_solve(gm_solver* s, gm_result* out) {
   if (!s || !out) return fail(GM_EINVAL, "bad argument");
   s->solved = false;
-  const int rc = solver_solve(s, out);
+  memset(out, 0, sizeof *out);
+  const int rc = solve_by_mode({s}, out);
   s->solved = rc == 0;  // (GM_PARTIAL: stopped early, the table is not finished)
   return rc;
 }
-
-static int solver_solve(gm_solver* s, gm_result* out) {
-  memset(out, 0, sizeof *out);
-  if (s->mode == GM_MODE_DENSE) return solve_dense(s, out);
-  if (s->mode == GM_MODE_PLANES) return run_planes({s}, out);
-  if (s->mode == GM_MODE_RANKED) return s->world > 1 ? run_ranked_shards({s}, out) : run_ranked(s, out);
-  if (s->mode == GM_MODE_BUCKETED) return s->world > 1 ? run_bucketed_shards({s}, out) : solve_bucketed(s, out);
-  if (s->world > 1) return fail(GM_EINVAL, "keyed-table shard %d/%d: drive it with gm_ks_* (md5 exchange)", s->rank, s->world);
-  const int T = s->d.max_levels;
-  // steps [first, stop) of the 2T (gm_solver_set_steps); forward level L is
-  // step L (level T-1 expands nothing), backward level L is step 2T-1-L
-  const int first = (int)s->step_first, stop = s->step_stop ? (int)s->step_stop : 2 * T;
-  s->step_first = s->step_stop = 0;
-  const bool timing = (s->flags & GM_F_KERNEL_TIMING) && first == 0 && stop == 2 * T;
-  std::vector<hipEvent_t> ev;
-  auto new_event = [&](hipEvent_t* e) -> int {
-    HIPCHK(hipEventCreate(e));
-    ev.push_back(*e);
-    return 0;
-  };
-  hipEvent_t e0, e1, e2;
-  if (new_event(&e0) || new_event(&e1) || new_event(&e2)) return GM_EHIP;
-  std::vector<hipEvent_t> kx, kr;  // per-launch start/stop pairs
-  if (timing) {
-    kx.resize(2 * (size_t)T);
-    kr.resize(2 * (size_t)T);
-    for (auto& e : kx)
-      if (new_event(&e)) return GM_EHIP;
-    for (auto& e : kr)
-      if (new_event(&e)) return GM_EHIP;
-  }
-  auto t0 = std::chrono::steady_clock::now();
-  HIPCHK(hipEventRecord(e0, s->stream));
-  if (first == 0) {
-    // fresh table: keys EMPTY, words NO_WORD
-    HIPCHK(hipMemsetAsync(s->tab, 0xFF, (s->mask + 1) * sizeof(gm_slot), s->stream));
-    HIPCHK(hipMemsetAsync(s->st, 0, devstate_bytes(T), s->stream));
-    hipLaunchKernelGGL(k_seed, dim3(1), dim3(64), 0, s->stream, s->tab, s->mask, s->lv, s->st, s->d.root);
-  }
-  for (int L = std::max(first, 0); L + 1 < T && L < stop; L++) {
-    if (timing) HIPCHK(hipEventRecord(kx[2 * L], s->stream));
-    do_expand(s, L);
-    if (timing) HIPCHK(hipEventRecord(kx[2 * L + 1], s->stream));
-    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, s->stream, s->st, L, s->lcap);
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(e1, s->stream));
-  for (int L = T - 1; L >= 0; L--) {
-    const int k = 2 * T - 1 - L;
-    if (k < first) continue;
-    if (k >= stop) break;
-    if (timing) HIPCHK(hipEventRecord(kr[2 * L], s->stream));
-    do_resolve(s, L);
-    if (timing) HIPCHK(hipEventRecord(kr[2 * L + 1], s->stream));
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(e2, s->stream));
-  if (stop < 2 * T) {  // stopped early: the state stays on the device for a resume
-    HIPCHK(hipStreamSynchronize(s->stream));
-    for (auto e : ev) (void)hipEventDestroy(e);
-    out->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return GM_PARTIAL;
-  }
-  hipLaunchKernelGGL(k_root_word, dim3(1), dim3(64), 0, s->stream, s->tab, s->mask, s->d.root, s->st);
-  HIPCHK(hipGetLastError());
-  std::vector<unsigned char> host(devstate_bytes(T));
-  HIPCHK(hipMemcpyAsync(host.data(), s->st, host.size(), hipMemcpyDeviceToHost, s->stream));
-  HIPCHK(hipStreamSynchronize(s->stream));
-  auto t1 = std::chrono::steady_clock::now();
-  const DevState* hs = (const DevState*)host.data();
-  const uint32_t word = hs->root_word;
-  float f = 0, b = 0;
-  HIPCHK(hipEventElapsedTime(&f, e0, e1));
-  HIPCHK(hipEventElapsedTime(&b, e1, e2));
-  out->ms_forward = f;
-  out->ms_backward = b;
-  out->ms_total = std::chrono::duration<double, std::milli>(t1 - t0).count();
-  if (timing) {
-    double sx = 0, sr = 0;
-    for (int L = 0; L + 1 < T; L++) {
-      float ms = 0;
-      HIPCHK(hipEventElapsedTime(&ms, kx[2 * L], kx[2 * L + 1]));
-      sx += ms;
-    }
-    for (int L = 0; L < T; L++) {
-      float ms = 0;
-      HIPCHK(hipEventElapsedTime(&ms, kr[2 * L], kr[2 * L + 1]));
-      sr += ms;
-    }
-    out->ms_expand_kernels = sx;
-    out->ms_resolve_kernels = sr;
-    out->n_expand_launches = (uint64_t)(T - 1);
-    out->n_resolve_launches = (uint64_t)T;
-  }
-  for (auto e : ev) (void)hipEventDestroy(e);
-  out->positions = hs->cursor_front + hs->cursor_back;
-  out->edges = hs->edges;
-  out->primitives = hs->prims;
-  out->max_level_width = (uint32_t)std::max<u64>(hs->max_width, 1);
-  uint32_t lv = 0;
-  for (int L = 0; L < T; L++) {
-    const LevelSeg& g = hs->seg[L];
-    if ((g.fe - g.fb) + (g.c2hi - g.c2lo) > 0) lv++;
-  }
-  out->levels = lv;
-  out->root_word = word;
-  if (hs->err) {
-    bool full = hs->err & (ERR_TABLE_FULL | ERR_LEVELS_FULL);
-    return fail(full ? GM_EFULL : GM_ECORRUPT, "solve failed:%s", err_text(hs->err).c_str());
-  }
-  if (word == NO_WORD) return fail(GM_ECORRUPT, "root unresolved");
-  out->root_value = (int32_t)(word & 3u);
-  out->root_remoteness = word >> 2;
-  return 0;
-}
-
-// the per-block counts summed into the table's totals and the solve's
-// reduction words (one block of 1024 threads; also the tail of the PLANES
-// finish kernel, k_plane_finish)
-__device__ __forceinline__ void fill_red_body(DevState* st, const BlockCount* bc) {
-  __shared__ u64 rn[16], re[16];
-  u64 sn = 0, se = 0;
-  for (int i = (int)threadIdx.x; i < kCountSlots; i += (int)blockDim.x) {
-    sn += bc[i].npos;
-    se += bc[i].edges;
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    sn += __shfl_xor(sn, o);
-    se += __shfl_xor(se, o);
-  }
-  if (__lane_id() == 0) {
-    rn[threadIdx.x >> 6] = sn;
-    re[threadIdx.x >> 6] = se;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    sn = se = 0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); w++) {
-      sn += rn[w];
-      se += re[w];
-    }
-    st->cursor_front += sn;  // this table's totals (gm_solver_positions reads them)
-    st->edges += se;
-    st->red[0] = st->cursor_front;
-    st->red[1] = st->edges;
-    st->red[2] = st->prims;
-    st->red[3] = st->root_word == NO_WORD ? 0 : (u64)st->root_word + 1;
-    st->red[4] = st->err;
-  }
-}
-__global__ __launch_bounds__(1024) void k_fill_red(DevState* st, const BlockCount* bc) { fill_red_body(st, bc); }
-
-// Band of level L: every non-hole slot has digit sum s(p) in [S - H0, S]
-// (S = root_sum - L), so its prefix lies between the smallest prefix with
-// s >= S - H0 (fill the low digits first) and the largest with s <= S (fill
-// the high digits first).  Narrowing a launch to the band skips whole
-// stretches of holes at both ends of the tier sequence.  Returns the view
-// clipped to the band (64-aligned start) or one with p_lo == p_hi.
-static DenseView dense_band(const Desc& d, const DenseView& v, u64 L) {
-  const int64_t S = (int64_t)d.root_sum - (int64_t)L;
-  int64_t T = S - (int64_t)d.heap[0];
-  u64 pmin = 0, pmax = 0;
-  int64_t rem = S;
-  for (int i = d.nheaps - 1; i >= 1; i--) {
-    const int64_t h = std::min<int64_t>(rem, d.heap[i]);
-    pmax += (u64)h * d.pstride[i];
-    rem -= h;
-  }
-  for (int i = 1; i < d.nheaps && T > 0; i++) {
-    const int64_t h = std::min<int64_t>(T, d.heap[i]);
-    pmin += (u64)h * d.pstride[i];
-    T -= h;
-  }
-  DenseView b = v;
-  if (S < 0 || T > 0) {  // no slot of this level exists
-    b.p_hi = b.p_lo;
-    return b;
-  }
-  b.p_lo = std::max<u64>(v.p_lo, pmin & ~63ull);
-  b.p_hi = std::min<u64>(v.p_hi, pmax + 1);
-  if (b.p_hi < b.p_lo) b.p_hi = b.p_lo;
-  return b;
-}
-
-// Halo exchanges of a dense shard group (block layout, DenseView).  Block
-// k's bottom two own slices (top values kB, kB+1) are the upper halo of
-// block k-1 (reach bits, after the pull); its top two own slices are the
-// lower halo of block k+1 (words, after the resolve).  With blocks dealt
-// round robin every block of rank r sends to the same neighbour rank
-// (r -/+ 1 mod world), in block order, and the receiver walks its blocks in
-// the same order.  Only the part of a slice pair inside level L's band
-// travels: bits as whole 64-bit words, words packed to their non-hole slots
-// (power-of-two tables, k_halo_move) or as the band's 4-B run.  `cs` is the
-// stream the copies / RCCL calls run on.  mode: 1 = RCCL (one process per
-// GPU), 2 = in-process group (device-to-device copies).
-
-// local slice index of slice o of local block j
-static u64 blk_slice(const gm_solver* s, u64 j, u64 o) { return j * (s->view.B + 4) + o; }
-// global top value of slice o of local block j
-static int64_t blk_top(const gm_solver* s, u64 j, u64 o) {
-  return (int64_t)(((u64)s->view.rank + j * s->view.world) * s->view.B + o) - 2;
-}
-static u64 blk_count(const gm_solver* s) { return s->view.Wl / ((s->view.B + 4) * s->view.Z); }
-static u64 blk_global(const gm_solver* s, u64 j) { return (u64)s->view.rank + j * s->view.world; }
-
-// prefixes [lo, hi) (offsets inside the slice pair starting at top value
-// t0) of level L's band; false if none
-static bool band_pair(const gm_solver* s, u64 L, int64_t t0, u64* lo, u64* hi) {
-  const DenseView all{0, ~0ull, 0, 0, 0};
-  const DenseView band = dense_band(s->d, all, L);
-  const int64_t Z = (int64_t)s->view.Z;
-  const int64_t a = std::max<int64_t>(t0 * Z, (int64_t)band.p_lo);
-  const int64_t b = std::min<int64_t>((t0 + 2) * Z, (int64_t)std::min<u64>(band.p_hi, (u64)INT64_MAX));
-  if (b <= a) return false;
-  *lo = (u64)(a - t0 * Z);
-  *hi = (u64)(b - t0 * Z);
-  return true;
-}
-
-static int xfer_call(gm_solver* s, int op, const void* sb, u64 sn, int sp, void* rb, u64 rn, int rp) {
-  const int rc = s->xfer(s->xfer_ctx, op, sb, sn, sp, rb, rn, rp);
-  return rc ? fail(GM_EHIP, "transport callback failed (%d) on rank %d", rc, s->rank) : 0;
-}
-// host-staged copy of device ranges into / out of s->hstage
-struct HostRange {
-  void* dev;
-  u64 bytes;
-};
-static int stage_out(gm_solver* s, const std::vector<HostRange>& rs, u64 at, hipStream_t cs) {
-  for (const HostRange& r : rs) {
-    HIPCHK(hipMemcpyAsync(s->hstage.data() + at, r.dev, r.bytes, hipMemcpyDeviceToHost, cs));
-    at += r.bytes;
-  }
-  HIPCHK(hipStreamSynchronize(cs));
-  return 0;
-}
-static int stage_in(gm_solver* s, const std::vector<HostRange>& rs, u64 at, hipStream_t cs) {
-  for (const HostRange& r : rs) {
-    HIPCHK(hipMemcpyAsync(r.dev, s->hstage.data() + at, r.bytes, hipMemcpyHostToDevice, cs));
-    at += r.bytes;
-  }
-  HIPCHK(hipStreamSynchronize(cs));
-  return 0;
-}
-static u64 ranges_bytes(const std::vector<HostRange>& rs) {
-  u64 n = 0;
-  for (const HostRange& r : rs) n += r.bytes;
-  return n;
-}
-// one paired transfer through the host: send ranges `out` to rank sp, receive
-// ranges `in` from rank rp
-static int xfer_ranges(gm_solver* s, const std::vector<HostRange>& out, int sp, const std::vector<HostRange>& in, int rp,
-                       hipStream_t cs) {
-  const u64 ns = ranges_bytes(out), nr = ranges_bytes(in);
-  if (s->hstage.size() < ns + nr) s->hstage.resize(ns + nr);
-  int rc = stage_out(s, out, 0, cs);
-  if (rc) return rc;
-  rc = xfer_call(s, GM_XFER_SENDRECV, s->hstage.data(), ns, sp, s->hstage.data() + ns, nr, rp);
-  if (rc) return rc;
-  return stage_in(s, in, ns, cs);
-}
-
-#include "gm_plane_run.h"
-#include "gm_ranked.h"
-#include "gm_ranked_shard.h"
-
-int gm_rk_shard_stats(gm_solver* s, uint64_t out[2]) {
-  if (!s || !out) return fail(GM_EINVAL, "bad argument");
-  if (s->mode != GM_MODE_RANKED || s->world < 2 || !s->rko_own) return fail(GM_EINVAL, "not a ranked md5 shard");
-  HIPCHK(hipStreamSynchronize(s->stream));
-  HIPCHK(hipMemcpy(&out[0], &s->st->ks_cursor, sizeof(u64), hipMemcpyDeviceToHost));
-  out[1] = 0;
-  for (size_t L = 0; L < s->rko_tot_h.size() / (size_t)s->world; L++) out[1] += s->rko_tot_h[L * s->world + s->rank];
-  return 0;
-}
-
-int gm_plane_halo_plan(int game, int rank, int world, uint32_t flags, uint64_t* out, uint32_t levels) {
-  const Desc* d = get_game(game);
-  if (!d || !out || world < 2 || rank < 0 || rank >= world) return fail(GM_EINVAL, "bad argument");
-  if (!plane_ok(d, world)) return fail(GM_EINVAL, "game has no planes layout");
-  PlaneShape ps;
-  int rc = plane_shape(d, rank, world, flags, &ps);
-  if (rc) return rc;
-  const uint32_t steps = ps.stage_k ? ps.nrows : ps.S + 1;
-  if (levels < steps) return fail(GM_EINVAL, "out holds %u steps, the plan has %u", levels, steps);
-  memset(out, 0, (size_t)levels * world * 2 * sizeof(uint64_t));
-  std::unique_ptr<gm_solver> s(new gm_solver());
-  s->world = world;
-  s->rank = rank;
-  std::vector<uint8_t> lb;
-  rc = plane_lists(s.get(), ps, lb);
-  if (rc) return rc;
-  if (ps.stage_k) {  // staged: step = halo row, to rank + 1 / from rank - 1
-    for (uint32_t r = 0; r < ps.nrows; r++) {
-      if (rank + 1 < world) out[((size_t)r * world + rank + 1) * 2] = s->psnd_off[r + 1] - s->psnd_off[r];
-      if (rank > 0) out[((size_t)r * world + rank - 1) * 2 + 1] = s->prcv_off[r + 1] - s->prcv_off[r];
-    }
-    return 0;
-  }
-  for (uint32_t l = 0; l <= ps.S; l++)
-    for (int p = 0; p < world; p++) {
-      u64 n;
-      plane_seg(s->psnd_off, l, world, p, &n);
-      out[((size_t)l * world + p) * 2] = n;
-      plane_seg(s->prcv_off, l, world, p, &n);
-      out[((size_t)l * world + p) * 2 + 1] = n;
-    }
-  return 0;
-}
-
-// after pull(L): bits of every block's bottom two own slices go down
-static int exchange_bits(std::vector<gm_solver*>& ss, u64 L, int mode, hipStream_t cs) {
-  auto bits_at = [&](gm_solver* s, u64 j, u64 o, u64 off) {
-    return s->bits + (L * s->view.Wbl + blk_slice(s, j, o) * s->view.Z + off) / 64;
-  };
-  if (mode == 3) {  // host-staged: the same ranges, in the same order as the RCCL form
-    gm_solver* s = ss[0];
-    const int down = (s->rank + s->world - 1) % s->world, up = (s->rank + 1) % s->world;
-    const u64 nb = blk_count(s), B = s->view.B;
-    std::vector<HostRange> out, in;
-    for (u64 j = 0; j < nb; j++) {
-      u64 lo, hi;
-      if (blk_global(s, j) >= 1 && band_pair(s, L, blk_top(s, j, 2), &lo, &hi)) {
-        lo &= ~63ull;
-        hi = (hi + 63) & ~63ull;
-        out.push_back({bits_at(s, j, 2, lo), (hi - lo) / 8});
-      }
-      if (blk_global(s, j) + 1 < s->nblocks && band_pair(s, L, blk_top(s, j, B + 2), &lo, &hi)) {
-        lo &= ~63ull;
-        hi = (hi + 63) & ~63ull;
-        in.push_back({bits_at(s, j, B + 2, lo), (hi - lo) / 8});
-      }
-    }
-    return xfer_ranges(s, out, down, in, up, cs);
-  }
-  if (mode == 1) {
-    gm_solver* s = ss[0];
-    const int down = (s->rank + s->world - 1) % s->world, up = (s->rank + 1) % s->world;
-    const u64 nb = blk_count(s), B = s->view.B;
-    RCCL_LIVE(s);
-    ncclGroupStart();
-    for (u64 j = 0; j < nb; j++) {
-      u64 lo, hi;
-      if (blk_global(s, j) >= 1 && band_pair(s, L, blk_top(s, j, 2), &lo, &hi)) {  // to block k-1
-        lo &= ~63ull;
-        hi = (hi + 63) & ~63ull;
-        ncclSend(bits_at(s, j, 2, lo), (hi - lo) / 8, ncclUint8, down, s->comm, cs);
-      }
-    }
-    for (u64 j = 0; j < nb; j++) {
-      u64 lo, hi;
-      if (blk_global(s, j) + 1 < s->nblocks && band_pair(s, L, blk_top(s, j, B + 2), &lo, &hi)) {  // from block k+1
-        lo &= ~63ull;
-        hi = (hi + 63) & ~63ull;
-        ncclRecv(bits_at(s, j, B + 2, lo), (hi - lo) / 8, ncclUint8, up, s->comm, cs);
-      }
-    }
-    ncclResult_t r = ncclGroupEnd();
-    if (r != ncclSuccess) return fail(GM_EHIP, "RCCL bits halo: %s", ncclGetErrorString(r));
-    return 0;
-  }
-  const int W = (int)ss.size();
-  for (gm_solver* s : ss) {
-    const u64 nb = blk_count(s), B = s->view.B;
-    for (u64 j = 0; j < nb; j++) {
-      const u64 k = blk_global(s, j);
-      u64 lo, hi;
-      if (k < 1 || !band_pair(s, L, blk_top(s, j, 2), &lo, &hi)) continue;
-      gm_solver* dst = ss[(k - 1) % W];
-      const u64 jd = (k - 1) / W;
-      lo &= ~63ull;
-      hi = (hi + 63) & ~63ull;
-      HIPCHK(hipMemcpyAsync(bits_at(dst, jd, B + 2, lo), bits_at(s, j, 2, lo), (hi - lo) / 8,
-                            hipMemcpyDeviceToDevice, cs));
-    }
-  }
-  return 0;
-}
-
-// packed halo helpers: non-hole words of the slice pair whose first slice
-// has top value t0 at level L
-static uint32_t halo_total(const gm_solver* s, int64_t x) {
-  return (x < 0 || x >= s->hg.XN) ? 0u : s->halo_tot[(size_t)x];
-}
-static uint32_t halo_count(const gm_solver* s, u64 L, int64_t t0) {
-  const int64_t x0 = (int64_t)s->d.root_sum - (int64_t)L - t0;
-  return halo_total(s, x0) + halo_total(s, x0 - 1);
-}
-// Pack (send side: every block's top pair, o = B) or unpack (receive side:
-// every block's lower halo, o = 0) all of a rank's halo pairs of level L
-// between the table and buf; returns the words moved.  Blocks without a
-// neighbour on that side are skipped, in the same order on both ends.
-static u64 halo_move_all(gm_solver* s, u64 L, int pack, uint32_t* buf, hipStream_t cs) {
-  const u64 nb = blk_count(s), B = s->view.B;
-  const int64_t S = (int64_t)s->d.root_sum - (int64_t)L;
-  const int H0 = (int)s->d.heap[0];
-  HaloColJobs J;
-  J.n = 0;
-  J.cum[0] = 0;
-  u64 at = 0;
-  auto flush = [&]() {
-    if (!J.n) return;
-    const u64 units = (u64)J.cum[J.n] * 64;
-    const int grid = (int)std::min<u64>(((units + kBlock - 1) / kBlock + 7) & ~7ull, (u64)s->grid);
-    uint32_t* lw = s->words + L * s->view.Wl;
-    uint16_t* lw16 = (uint16_t*)s->words + L * s->view.Wl;
-    if (s->w16) {  // two columns per wave, eight slots per lane
-      const u64 u2 = (u64)((J.cum[J.n] + 1) / 2) * 64;
-      const int g2 = (int)std::min<u64>(((u2 + kBlock - 1) / kBlock + 7) & ~7ull, (u64)s->grid);
-      if (pack)
-        hipLaunchKernelGGL((k_halo_cols16<true>), dim3(g2), dim3(kBlock), 0, cs, s->d, J, s->view.Z, s->colperm,
-                           s->ht, lw16, (uint16_t*)buf);
-      else
-        hipLaunchKernelGGL((k_halo_cols16<false>), dim3(g2), dim3(kBlock), 0, cs, s->d, J, s->view.Z, s->colperm,
-                           s->ht, lw16, (uint16_t*)buf);
-    } else if (pack && s->halo16)
-      hipLaunchKernelGGL((k_halo_cols<true, true>), dim3(grid), dim3(kBlock), 0, cs, s->d, J, s->view.Z, s->colperm,
-                         s->ht, lw, (void*)buf);
-    else if (pack)
-      hipLaunchKernelGGL((k_halo_cols<true, false>), dim3(grid), dim3(kBlock), 0, cs, s->d, J, s->view.Z, s->colperm,
-                         s->ht, lw, (void*)buf);
-    else if (s->halo16)
-      hipLaunchKernelGGL((k_halo_cols<false, true>), dim3(grid), dim3(kBlock), 0, cs, s->d, J, s->view.Z, s->colperm,
-                         s->ht, lw, (void*)buf);
-    else
-      hipLaunchKernelGGL((k_halo_cols<false, false>), dim3(grid), dim3(kBlock), 0, cs, s->d, J, s->view.Z,
-                         s->colperm, s->ht, lw, (void*)buf);
-    J.n = 0;
-  };
-  for (u64 j = 0; j < nb; j++) {
-    const u64 k = blk_global(s, j);
-    if (pack ? k + 1 >= s->nblocks : k < 1) continue;
-    const u64 o = pack ? B : 0;
-    for (u64 m = 0; m < 2; m++) {
-      const int64_t t = blk_top(s, j, o + m), x = S - t;
-      const uint32_t n = halo_total(s, x);
-      if (!n) continue;
-      // live columns of slice x: sums gs in [x - heap0 - mj, x]
-      const int64_t glo = std::max<int64_t>(0, x - H0 - s->hg.mj), ghi = std::min<int64_t>(x, s->hg.NG - 2);
-      const uint32_t ca = s->cstart[(size_t)glo], cb = s->cstart[(size_t)ghi + 1];
-      if (J.n == (uint32_t)kMaxHaloColJobs) flush();
-      J.lo[J.n] = ca;
-      J.u[J.n] = (uint32_t)blk_slice(s, j, o + m);
-      J.x[J.n] = (int32_t)x;
-      J.base[J.n] = (uint32_t)at;
-      J.cum[J.n + 1] = J.cum[J.n] + (cb - ca);
-      J.n++;
-      at += n;
-    }
-  }
-  flush();
-  return at;
-}
-static u64 halo_recv_count(const gm_solver* s, u64 L) {
-  u64 n = 0;
-  for (u64 j = 0; j < blk_count(s); j++)
-    if (blk_global(s, j) >= 1) n += halo_count(s, L, blk_top(s, j, 0));
-  return n;
-}
-// words halo_move_all packs on the send side (its count, without the kernels)
-static u64 halo_send_count(const gm_solver* s, u64 L) {
-  u64 n = 0;
-  for (u64 j = 0; j < blk_count(s); j++)
-    if (blk_global(s, j) + 1 < s->nblocks) n += halo_count(s, L, blk_top(s, j, s->view.B));
-  return n;
-}
-
-// Fail-fast check of a sharded solve's exchange plan.  Every message of
-// every level is fixed by the geometry, so before level 0 each rank
-// fingerprints, per level, the ordered byte counts it will send and receive
-// for the bits (down) and words (up) halos; the fingerprints are gathered
-// and a sender's must equal its receiver's.  A mismatch -- which under RCCL
-// would leave a receive of the wrong size waiting forever -- is GM_ECORRUPT
-// on every rank at once, before any transfer.
-struct SigAcc {
-  u64 h = 1469598103934665603ull, n = 0;
-  void add(u64 bytes) {
-    h = (h ^ bytes) * 1099511628211ull;
-    n++;
-  }
-  u64 get() const { return h ^ (n << 56); }
-};
-static void halo_sigs(const gm_solver* s, u64 L, u64 out[4]) {
-  SigAcc bs, br, ws, wr;
-  const u64 nb = blk_count(s), B = s->view.B;
-  for (u64 j = 0; j < nb; j++) {
-    u64 lo, hi;
-    if (blk_global(s, j) >= 1 && band_pair(s, L, blk_top(s, j, 2), &lo, &hi))
-      bs.add(((hi + 63) & ~63ull) / 8 - (lo & ~63ull) / 8);
-    if (blk_global(s, j) + 1 < s->nblocks && band_pair(s, L, blk_top(s, j, B + 2), &lo, &hi))
-      br.add(((hi + 63) & ~63ull) / 8 - (lo & ~63ull) / 8);
-  }
-  if (s->hg.on) {
-    const u64 wb = s->halo16 ? 2 : 4;
-    const u64 ns = halo_send_count(s, L), nr = halo_recv_count(s, L);
-    if (ns) ws.add(ns * wb);
-    if (nr) wr.add(nr * wb);
-  } else {
-    for (u64 j = 0; j < nb; j++) {
-      u64 lo, hi;
-      if (blk_global(s, j) + 1 < s->nblocks && band_pair(s, L, blk_top(s, j, B), &lo, &hi)) ws.add((hi - lo) * 4);
-      if (blk_global(s, j) >= 1 && band_pair(s, L, blk_top(s, j, 0), &lo, &hi)) wr.add((hi - lo) * 4);
-    }
-  }
-  out[0] = bs.get();
-  out[1] = br.get();
-  out[2] = ws.get();
-  out[3] = wr.get();
-}
-// all ranks' fingerprints, rank-major [world][T][4]: bits go down (rank r
-// sends what r - 1 receives), words go up
-static int halo_sigs_match(const std::vector<u64>& all, int world, int T) {
-  auto at = [&](int r, int L, int k) { return all[((size_t)r * T + L) * 4 + k]; };
-  for (int r = 0; r < world; r++) {
-    const int down = (r + world - 1) % world, up = (r + 1) % world;
-    for (int L = 0; L < T; L++) {
-      if (at(r, L, 0) != at(down, L, 1))
-        return fail(GM_ECORRUPT, "bits halo of level %d: rank %d would send what rank %d does not expect", L, r, down);
-      if (at(r, L, 2) != at(up, L, 3))
-        return fail(GM_ECORRUPT, "words halo of level %d: rank %d would send what rank %d does not expect", L, r, up);
-    }
-  }
-  return 0;
-}
-// gather every rank's fingerprints and compare (once per solver: the
-// geometry never changes)
-static int check_halo_plan(std::vector<gm_solver*>& ss, int mode, hipStream_t st) {
-  gm_solver* s0 = ss[0];
-  if (s0->halo_ok) return 0;
-  const int T = s0->d.max_levels, W = s0->world;
-  std::vector<u64> all((size_t)W * T * 4);
-  if (mode == 2) {
-    for (gm_solver* s : ss)
-      for (int L = 0; L < T; L++) halo_sigs(s, (u64)L, &all[((size_t)s->rank * T + L) * 4]);
-  } else {
-    std::vector<u64> mine((size_t)T * 4);
-    for (int L = 0; L < T; L++) halo_sigs(s0, (u64)L, &mine[(size_t)L * 4]);
-    if (mode == 3) {
-      int rc = xfer_call(s0, GM_XFER_ALLGATHER, mine.data(), mine.size() * 8, -1, all.data(), all.size() * 8, -1);
-      if (rc) return rc;
-    } else {
-      void* dev = nullptr;
-      HIPCHK(hipMalloc(&dev, (all.size() + mine.size()) * 8));
-      u64* dall = (u64*)dev;
-      u64* dmine = dall + all.size();
-      hipError_t e = hipMemcpyAsync(dmine, mine.data(), mine.size() * 8, hipMemcpyHostToDevice, st);
-      ncclResult_t r = ncclSuccess;
-      if (s0->gabort && s0->gabort->load(std::memory_order_acquire)) r = ncclInvalidUsage;
-      if (e == hipSuccess && r == ncclSuccess) r = ncclAllGather(dmine, dall, mine.size(), ncclUint64, s0->comm, st);
-      if (e == hipSuccess && r == ncclSuccess) e = hipMemcpyAsync(all.data(), dall, all.size() * 8, hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipStreamSynchronize(st);
-      (void)hipFree(dev);
-      if (r != ncclSuccess) return fail(GM_EHIP, "RCCL allgather of the halo plan: %s", ncclGetErrorString(r));
-      if (e != hipSuccess) return fail(GM_EHIP, "halo plan: %s", hipGetErrorString(e));
-    }
-  }
-  int rc = halo_sigs_match(all, W, T);
-  if (rc) return rc;
-  for (gm_solver* s : ss) s->halo_ok = true;
-  return 0;
-}
-
-// after resolve(L): words of every block's top two own slices go up.
-// Power-of-two tables send only the non-hole words (about a fifth of the
-// two slices, averaged over the levels).
-static int exchange_words(std::vector<gm_solver*>& ss, u64 L, int mode, hipStream_t cs) {
-  bool packed = true;
-  for (gm_solver* s : ss) packed = packed && s->hg.on;
-  auto words_at = [&](gm_solver* s, u64 j, u64 o, u64 off) {
-    return s->words + L * s->view.Wl + blk_slice(s, j, o) * s->view.Z + off;
-  };
-  if (mode == 3) {  // host-staged: the RCCL form's buffers and order
-    gm_solver* s = ss[0];
-    const int down = (s->rank + s->world - 1) % s->world, up = (s->rank + 1) % s->world;
-    const u64 nb = blk_count(s), B = s->view.B;
-    std::vector<HostRange> out, in;
-    u64 nrecv = 0;
-    if (packed) {
-      const u64 wb = s->halo16 ? 2 : 4;
-      const u64 nsend = halo_move_all(s, L, 1, s->halo_send, cs);
-      HIPCHK(hipGetLastError());
-      nrecv = halo_recv_count(s, L);
-      if (nsend) out.push_back({s->halo_send, nsend * wb});
-      if (nrecv) in.push_back({s->halo_recv, nrecv * wb});
-    } else {
-      for (u64 j = 0; j < nb; j++) {
-        u64 lo, hi;
-        if (blk_global(s, j) + 1 < s->nblocks && band_pair(s, L, blk_top(s, j, B), &lo, &hi))
-          out.push_back({words_at(s, j, B, lo), (hi - lo) * 4});
-        if (blk_global(s, j) >= 1 && band_pair(s, L, blk_top(s, j, 0), &lo, &hi))
-          in.push_back({words_at(s, j, 0, lo), (hi - lo) * 4});
-      }
-    }
-    int rc = xfer_ranges(s, out, up, in, down, cs);
-    if (rc) return rc;
-    if (packed && nrecv) halo_move_all(s, L, 0, s->halo_recv, cs);
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  if (mode == 1) {
-    gm_solver* s = ss[0];
-    const int down = (s->rank + s->world - 1) % s->world, up = (s->rank + 1) % s->world;
-    const u64 nb = blk_count(s), B = s->view.B;
-    RCCL_LIVE(s);
-    if (packed) {
-      const u64 nsend = halo_move_all(s, L, 1, s->halo_send, cs);
-      const u64 nrecv = halo_recv_count(s, L);
-      ncclGroupStart();
-      const u64 wb = s->halo16 ? 2 : 4;  // bytes per packed word
-      if (nsend) ncclSend(s->halo_send, nsend * wb, ncclUint8, up, s->comm, cs);
-      if (nrecv) ncclRecv(s->halo_recv, nrecv * wb, ncclUint8, down, s->comm, cs);
-      ncclResult_t r = ncclGroupEnd();
-      if (r != ncclSuccess) return fail(GM_EHIP, "RCCL words halo: %s", ncclGetErrorString(r));
-      if (nrecv) halo_move_all(s, L, 0, s->halo_recv, cs);
-      HIPCHK(hipGetLastError());
-      return 0;
-    }
-    ncclGroupStart();
-    for (u64 j = 0; j < nb; j++) {
-      u64 lo, hi;
-      if (blk_global(s, j) + 1 < s->nblocks && band_pair(s, L, blk_top(s, j, B), &lo, &hi))
-        ncclSend(words_at(s, j, B, lo), (hi - lo) * 4, ncclUint8, up, s->comm, cs);
-    }
-    for (u64 j = 0; j < nb; j++) {
-      u64 lo, hi;
-      if (blk_global(s, j) >= 1 && band_pair(s, L, blk_top(s, j, 0), &lo, &hi))
-        ncclRecv(words_at(s, j, 0, lo), (hi - lo) * 4, ncclUint8, down, s->comm, cs);
-    }
-    ncclResult_t r = ncclGroupEnd();
-    if (r != ncclSuccess) return fail(GM_EHIP, "RCCL words halo: %s", ncclGetErrorString(r));
-    return 0;
-  }
-  const int W = (int)ss.size();
-  if (packed) {
-    // every block of shard g sends to shard g + 1 (mod W): pack straight
-    // into the receiver's buffer, then unpack there -- the RCCL path's
-    // kernels and order, with the transfer left out
-    for (int g = 0; g < W; g++) {
-      gm_solver* dst = ss[(g + 1) % W];
-      const u64 n = halo_move_all(ss[g], L, 1, dst->halo_recv, cs);
-      // the RCCL path posts a receive of halo_recv_count words for the
-      // sender's count: a mismatch would hang it, so the group checks it
-      if (n != halo_recv_count(dst, L))
-        return fail(GM_ECORRUPT, "halo count mismatch at level %llu: shard %d packs %llu, shard %d expects %llu",
-                    (unsigned long long)L, g, (unsigned long long)n, (g + 1) % W,
-                    (unsigned long long)halo_recv_count(dst, L));
-      if (n) halo_move_all(dst, L, 0, dst->halo_recv, cs);
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  for (gm_solver* s : ss) {
-    const u64 nb = blk_count(s), B = s->view.B;
-    for (u64 j = 0; j < nb; j++) {
-      const u64 k = blk_global(s, j);
-      if (k + 1 >= s->nblocks) continue;
-      gm_solver* dst = ss[(k + 1) % W];
-      const u64 jd = (k + 1) / W;
-      const int64_t t0 = blk_top(s, j, B);
-      u64 lo, hi;
-      if (!band_pair(s, L, t0, &lo, &hi)) continue;
-      HIPCHK(hipMemcpyAsync(words_at(dst, jd, 0, lo), words_at(s, j, B, lo), (hi - lo) * 4,
-                            hipMemcpyDeviceToDevice, cs));
-    }
-  }
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// Dense solve of one table (world 1), one shard of an RCCL job, or every
-// shard of an in-process group (all on one stream), level-synchronously.
-static int run_dense(std::vector<gm_solver*> ss, gm_result* out) {
-  gm_solver* s0 = ss[0];
-  const Desc& d = s0->d;
-  const int T = d.max_levels;
-  // 0: one table; 1: one shard per process over RCCL; 2: in-process group;
-  // 3: one shard per process over a host-staged transport
-  const int mode = s0->world <= 1 ? 0 : ss.size() != 1 ? 2 : s0->xfer ? 3 : 1;
-  if (mode == 1 && !s0->comm) return fail(GM_EINVAL, "shard %d/%d has no communicator (gm_solver_comm_init)", s0->rank, s0->world);
-  if (mode == 2) {
-    if ((int)ss.size() != s0->world) return fail(GM_EINVAL, "group solve needs all %d shards", s0->world);
-    for (size_t g = 0; g < ss.size(); g++)
-      if (ss[g]->rank != (int)g || ss[g]->stream != s0->stream || ss[g]->mode != GM_MODE_DENSE)
-        return fail(GM_EINVAL, "group shards must be ranks 0..n-1 on one stream");
-  }
-  // steps [first, stop) (gm_solver_set_steps, world 1 only): forward level L
-  // is step L, backward level L is step 2T-1-L
-  const int first = mode == 0 ? (int)s0->step_first : 0;
-  const int stop = mode == 0 && s0->step_stop ? (int)s0->step_stop : 2 * T;
-  s0->step_first = s0->step_stop = 0;
-  const bool timing = (s0->flags & GM_F_KERNEL_TIMING) && first == 0 && stop == 2 * T;
-  hipStream_t st = s0->stream;
-  // the kernel families and word width were fixed at creation (dense_choose);
-  // a resume checks the interrupted solve used the same width
-  for (gm_solver* s : ss) {
-    s->launch_err = false;
-    if (first > 0) {
-      uint32_t wb = 0;
-      HIPCHK(hipMemcpy(&wb, &s->st->word_bits, sizeof wb, hipMemcpyDeviceToHost));
-      if (wb != 8 && wb != 16 && wb != 32) return fail(GM_EINVAL, "resume: scratch holds no solve in progress");
-      if (wb != s->wbits())
-        return fail(GM_EINVAL, "resume: the interrupted solve used %u-bit words, this solver %u", wb, s->wbits());
-    }
-  }
-  std::vector<hipEvent_t> ev;
-  auto new_event = [&](hipEvent_t* e) -> int {
-    HIPCHK(hipEventCreate(e));
-    ev.push_back(*e);
-    return 0;
-  };
-  hipEvent_t e0, e1, e2;
-  if (new_event(&e0) || new_event(&e1) || new_event(&e2)) return GM_EHIP;
-  std::vector<hipEvent_t> kx, kr;  // per-level kernel start/stop (shard 0's launches)
-  if (timing) {
-    kx.resize(2 * (size_t)T);
-    kr.resize(2 * (size_t)T);
-    for (auto& e : kx)
-      if (new_event(&e)) return GM_EHIP;
-    for (auto& e : kr)
-      if (new_event(&e)) return GM_EHIP;
-  }
-  const u64 root_p = d.root / d.base[0];  // global prefix of the root (level 0)
-  // launches cover only the level's band of prefixes (dense_band); the
-  // grid is a multiple of 8 blocks for the XCD-chunked kernels
-  auto grid_of = [&](gm_solver* s, const DenseView& b) {
-    const u64 blocks = (b.p_hi - b.p_lo + kBlock - 1) / kBlock;
-    return (int)std::min<u64>((blocks + 7) & ~7ull, (u64)s->grid);
-  };
-  auto t0 = std::chrono::steady_clock::now();
-  // Sharded solves overlap each level's halo exchange with compute: a
-  // level's launch is split into the part whose parents (pull) / children
-  // (resolve) lie inside the shard's own block -- which includes the two
-  // slices the exchange sends -- and the two boundary slices that read the
-  // halo.  Per level: own part -> event -> exchange on the comm stream ->
-  // event; the boundary part of the NEXT level waits for that exchange.  A
-  // block narrower than 4 top values has no such split: exchange in order.
-  bool pipe = mode == 1 || mode == 2;  // the host-staged transport runs in order
-  for (gm_solver* s : ss)
-    if (s->view.B < 4) pipe = false;
-  if (s0->flags & GM_F_SHARD_INORDER) pipe = false;  // A/B: exchange in order
-  hipStream_t cs = st;
-  hipEvent_t* E = nullptr;  // [0, T): own part done, [T, 2T): exchange done (forward); reused backward
-  if (pipe) {
-    if (!s0->cstream) HIPCHK(hipStreamCreateWithFlags(&s0->cstream, hipStreamNonBlocking));
-    while (s0->pev.size() < 2 * (size_t)T) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      s0->pev.push_back(e);
-    }
-    cs = s0->cstream;
-    E = s0->pev.data();
-  }
-  // the launch view of level L: world 1 sweeps the level's band; a shard
-  // sweeps its whole local range, processing the own slices o in [olo, ohi)
-  // of every block
-  int slow = 0;  // largest digit sum of the prefix digits below the top
-  for (int i = 1; i + 1 < d.nheaps; i++) slow += (int)d.heap[i];
-  auto level_view = [&](gm_solver* s, int L, uint32_t olo, uint32_t ohi) {
-    if (!s->view.blk) return dense_band(d, s->view, (u64)L);
-    // a shard sweeps only the listed slices of its blocks that hold a
-    // non-hole at level L: top value t with 0 <= S - t <= slow + heap0
-    DenseView c = s->view;
-    c.olo = olo;
-    c.ohi = ohi;
-    const int64_t S = (int64_t)d.root_sum - L;
-    uint32_t n = 0;
-    bool over = false;
-    for (u64 j = 0; j < blk_count(s); j++)
-      for (uint32_t o = olo; o < ohi; o++) {
-        const int64_t t = blk_top(s, j, o);
-        if (t < 0 || (u64)t >= c.E || S - t < 0 || S - t > slow + (int64_t)d.heap[0]) continue;
-        if (n == (uint32_t)kMaxSweepSlices || t > 0xFFFF || blk_slice(s, j, o) > 0xFFFF) {
-          over = true;
-        } else {
-          c.sl[n] = (uint16_t)blk_slice(s, j, o);
-          c.st[n++] = (uint16_t)t;
-        }
-      }
-    c.p_lo = 0;
-    if (over) {  // too many to list: sweep everything, filter per wave
-      c.nsl = 0;
-      c.p_hi = c.Wl;
-    } else {
-      c.nsl = n;
-      c.p_hi = (u64)n * c.Z;
-    }
-    return c;
-  };
-  if (mode != 0) {
-    int rc = check_halo_plan(ss, mode, st);
-    if (rc) return rc;
-  }
-  // Tail runs (one table, whole solves, live-group lists, 8-bit words): the
-  // levels at both ends whose live groups fit a workgroup in a pass or two
-  // run as one single-workgroup launch each (k_dense_pull_tail,
-  // k_dense_resolve16_tail).  A kernel-timing solve keeps one launch per
-  // level, so per-launch figures (bench roofline, PMC passes of a timed solve)
-  // describe the per-level kernels alone.
-  const bool tails = mode == 0 && !timing && first == 0 && stop == 2 * T && s0->glist && !s0->view.blk &&
-                     s0->pk == PK_WORDS && s0->w8 && d.pow2;
-  int pa = 0, pb = T, ra = T, rb = 0;  // per-level pulls [pa, pb); per-level resolves [rb, ra)
-  TailRun pull_head{}, pull_end{}, res_head{}, res_end{};
-  if (tails) {
-    auto groups = [&](int L) { return s0->goff[(size_t)L + 1] - s0->goff[(size_t)L]; };
-    auto add = [&](TailRun& R, int L) {
-      R.L[R.n] = (uint32_t)L;
-      R.off[R.n] = (uint32_t)s0->goff[(size_t)L];
-      R.cnt[R.n] = (uint32_t)groups(L);
-      R.phi[R.n] = dense_band(d, s0->view, (u64)L).p_hi;
-      R.n++;
-    };
-    while (pa < T && pa < kTailMax && groups(pa) <= kTailPullGroups) add(pull_head, pa++);
-    while (pb > pa && T - pb < kTailMax && groups(pb - 1) <= kTailPullGroups) pb--;
-    for (int L = pb; L < T; L++) add(pull_end, L);
-    while (ra > 0 && T - ra < kTailMax && groups(ra - 1) <= kTailResolveGroups) add(res_head, --ra);
-    while (rb < ra && rb < kTailMax && groups(rb) <= kTailResolveGroups) rb++;
-    for (int L = rb - 1; L >= 0; L--) add(res_end, L);
-  }
-  // forward (pull): level 0 .. T-1, each level's bitmap written exactly once.
-  // Parents are one or two top values ABOVE: the boundary is the top two
-  // slices [b-2, b), whose parents sit in the halo [b, b+2) sent down by the
-  // rank above.
-  auto issue_forward = [&]() -> int {
-  if (first == 0) {
-    for (gm_solver* s : ss) {
-      HIPCHK(hipMemsetAsync(s->st, 0, devstate_bytes(T), st));
-      HIPCHK(hipMemsetAsync(s->bcount, 0, kCountSlots * sizeof(BlockCount), st));
-      HIPCHK(hipMemsetD32Async((hipDeviceptr_t)&s->st->word_bits, (int)s->wbits(), 1, st));
-    }
-  }
-  dense_launch_tail(s0, pull_head, true, root_p);
-  for (int L = first; L < T && L < stop; L++) {
-    if (L < pa || L >= pb) continue;  // in a tail run
-    if (timing) HIPCHK(hipEventRecord(kx[2 * L], st));
-    for (gm_solver* s : ss) {
-      const uint32_t B = s->view.B;  // pull: the top two own slices read the upper halo
-      const DenseView own = level_view(s, L, 2, pipe ? B : B + 2);
-      if (own.p_hi > own.p_lo) dense_launch_pull(s, own, grid_of(s, own), (u64)L, root_p);
-    }
-    if (mode) {
-      if (pipe) {
-        HIPCHK(hipEventRecord(E[L], st));
-        HIPCHK(hipStreamWaitEvent(cs, E[L], 0));
-      }
-      int rc = exchange_bits(ss, (u64)L, mode, cs);
-      if (rc) return rc;
-      if (pipe) {
-        HIPCHK(hipEventRecord(E[T + L], cs));
-        if (L >= 1) HIPCHK(hipStreamWaitEvent(st, E[T + L - 1], 0));  // halos of L-1 (L-2 waited before)
-        for (gm_solver* s : ss) {
-          const DenseView bd = level_view(s, L, s->view.B, s->view.B + 2);
-          if (bd.p_hi > bd.p_lo) dense_launch_pull(s, bd, grid_of(s, bd), (u64)L, root_p);
-        }
-      }
-    }
-    if (timing) HIPCHK(hipEventRecord(kx[2 * L + 1], st));
-  }
-  dense_launch_tail(s0, pull_end, true, root_p);
-  HIPCHK(hipGetLastError());
-  return 0;
-  };
-  // backward (resolve): children are one or two top values BELOW: the
-  // boundary is the bottom two slices [a, a+2), whose children sit in the
-  // halo [a-2, a) sent up by the rank below.
-  auto issue_backward = [&]() -> int {
-  dense_launch_tail(s0, res_head, false, root_p);
-  for (int L = T - 1; L >= 0; L--) {
-    if (2 * T - 1 - L < first) continue;
-    if (2 * T - 1 - L >= stop) break;
-    if (L >= ra || L < rb) continue;  // in a tail run
-    if (timing) HIPCHK(hipEventRecord(kr[2 * L], st));
-    for (gm_solver* s : ss) {
-      const uint32_t B = s->view.B;  // resolve: the bottom two own slices read the lower halo
-      const DenseView own = level_view(s, L, pipe ? 4 : 2, B + 2);
-      if (own.p_hi > own.p_lo) dense_launch_resolve(s, own, grid_of(s, own), (u64)L);
-    }
-    if (mode) {
-      if (pipe) {
-        HIPCHK(hipEventRecord(E[L], st));
-        HIPCHK(hipStreamWaitEvent(cs, E[L], 0));
-      }
-      int rc = exchange_words(ss, (u64)L, mode, cs);
-      if (rc) return rc;
-      if (pipe) {
-        HIPCHK(hipEventRecord(E[T + L], cs));
-        if (L + 1 < T) HIPCHK(hipStreamWaitEvent(st, E[T + L + 1], 0));  // halos of L+1 (L+2 waited before)
-        for (gm_solver* s : ss) {
-          const DenseView bd = level_view(s, L, 2, 4);
-          if (bd.p_hi > bd.p_lo) dense_launch_resolve(s, bd, grid_of(s, bd), (u64)L);
-        }
-      }
-    }
-    if (timing) HIPCHK(hipEventRecord(kr[2 * L + 1], st));
-  }
-  dense_launch_tail(s0, res_end, false, root_p);
-  HIPCHK(hipGetLastError());
-  return 0;
-  };
-  // GM_F_GRAPH: one-table full solves replay HIP graphs of these launches,
-  // captured on the first such solve of the solver (every argument -- level
-  // views, group lists, XCD shares, tail runs, grids -- is fixed when the
-  // solver is made), so the host enqueues two graph launches instead of ~350
-  // kernels.  Measured on the bench workload: 4.47-4.49 ms against
-  // 4.44-4.48 ms with plain launches (the host already runs ahead of the
-  // GPU; what remains between levels is the device-side kernel boundary), so
-  // it is not the default.
-  const bool graphed = (s0->flags & GM_F_GRAPH) && mode == 0 && !timing && first == 0 && stop == 2 * T;
-  if (graphed && !s0->gfwd) {
-    auto capture = [&](auto&& issue, hipGraphExec_t* exec) -> int {
-      hipGraph_t g = nullptr;
-      HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-      const int rc = issue();
-      const hipError_t e = hipStreamEndCapture(st, &g);
-      if (rc || e != hipSuccess || s0->launch_err) {
-        if (g) (void)hipGraphDestroy(g);
-        return rc ? rc : e != hipSuccess ? fail(GM_EHIP, "graph capture: %s", hipGetErrorString(e)) : 0;
-      }
-      const hipError_t ei = hipGraphInstantiate(exec, g, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(g);
-      if (ei != hipSuccess) {
-        *exec = nullptr;
-        return fail(GM_EHIP, "graph instantiate: %s", hipGetErrorString(ei));
-      }
-      return 0;
-    };
-    int rc = capture(issue_forward, &s0->gfwd);
-    if (!rc) rc = capture(issue_backward, &s0->gbwd);
-    if (rc || !s0->gfwd || !s0->gbwd) {  // a launch error is reported by the plain path below
-      if (s0->gfwd) (void)hipGraphExecDestroy(s0->gfwd);
-      if (s0->gbwd) (void)hipGraphExecDestroy(s0->gbwd);
-      s0->gfwd = s0->gbwd = nullptr;
-      s0->launch_err = false;
-      if (rc) return rc;
-    }
-  }
-  const bool replay = graphed && s0->gfwd && s0->gbwd;
-  HIPCHK(hipEventRecord(e0, st));
-  if (replay) {
-    HIPCHK(hipGraphLaunch(s0->gfwd, st));
-  } else {
-    const int rc = issue_forward();
-    if (rc) return rc;
-  }
-  if (pipe) {  // the backward pass reuses the events: drain the forward exchanges first
-    HIPCHK(hipEventRecord(E[0], cs));
-    HIPCHK(hipStreamWaitEvent(st, E[0], 0));
-  }
-  HIPCHK(hipEventRecord(e1, st));
-  if (replay) {
-    HIPCHK(hipGraphLaunch(s0->gbwd, st));
-  } else {
-    const int rc = issue_backward();
-    if (rc) return rc;
-  }
-  if (pipe) {  // every exchange done before the reduction and the host read-back
-    HIPCHK(hipEventRecord(E[0], cs));
-    HIPCHK(hipStreamWaitEvent(st, E[0], 0));
-  }
-  HIPCHK(hipEventRecord(e2, st));
-  if (stop < 2 * T) {  // stopped early (world 1): the state stays on the device for a resume
-    HIPCHK(hipStreamSynchronize(st));
-    for (auto e : ev) (void)hipEventDestroy(e);
-    out->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    out->word_bits = s0->wbits();
-    return GM_PARTIAL;
-  }
-  for (gm_solver* s : ss) {
-    uint64_t root_q = ~0ull;
-    if (!dense_local(s->view, root_p, &root_q)) root_q = ~0ull;
-    hipLaunchKernelGGL(k_dense_root, dim3(1), dim3(64), 0, st, s->view, s->words, s->bits, root_q, s->st, s->wbits());
-    hipLaunchKernelGGL(k_fill_red, dim3(1), dim3(1024), 0, st, s->st, s->bcount);
-  }
-  if (mode == 1) {  // counts and root word summed; every rank's error mask gathered, OR-ed on the host
-    RCCL_LIVE(s0);
-    ncclGroupStart();
-    ncclResult_t r = ncclAllReduce(s0->st->red, s0->st->red, 4, ncclUint64, ncclSum, s0->comm, st);
-    ncclResult_t r2 = ncclAllGather(s0->st->red + 4, s0->errg, 1, ncclUint64, s0->comm, st);
-    ncclResult_t r3 = ncclGroupEnd();
-    if (r != ncclSuccess || r2 != ncclSuccess || r3 != ncclSuccess)
-      return fail(GM_EHIP, "RCCL allreduce: %s", ncclGetErrorString(r != ncclSuccess ? r : r2 != ncclSuccess ? r2 : r3));
-  }
-  // totals (host): RCCL has already reduced red[] across ranks; a group and
-  // the host-staged transport reduce here (counts summed, error masks OR-ed)
-  u64 red[5] = {0, 0, 0, 0, 0};
-  for (gm_solver* s : ss) {
-    u64 r[5];
-    HIPCHK(hipMemcpyAsync(r, s->st->red, sizeof r, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (mode == 3) {
-      std::vector<u64> all((size_t)5 * s->world);
-      int rc = xfer_call(s, GM_XFER_ALLGATHER, r, sizeof r, -1, all.data(), all.size() * 8, -1);
-      if (rc) return rc;
-      for (int g = 0; g < s->world; g++)
-        for (int i = 0; i < 5; i++) red[i] = (i == 4) ? (red[i] | all[(size_t)g * 5 + i]) : red[i] + all[(size_t)g * 5 + i];
-      continue;
-    }
-    if (mode == 1) {
-      std::vector<u64> e((size_t)s->world);
-      HIPCHK(hipMemcpy(e.data(), s->errg, e.size() * sizeof(u64), hipMemcpyDeviceToHost));
-      r[4] = 0;
-      for (u64 x : e) r[4] |= x;
-    }
-    for (int i = 0; i < 5; i++) red[i] = (i == 4) ? (red[i] | r[i]) : red[i] + r[i];
-  }
-  auto t1 = std::chrono::steady_clock::now();
-  float f = 0, b = 0;
-  HIPCHK(hipEventElapsedTime(&f, e0, e1));
-  HIPCHK(hipEventElapsedTime(&b, e1, e2));
-  out->ms_forward = f;
-  out->ms_backward = b;
-  out->ms_total = std::chrono::duration<double, std::milli>(t1 - t0).count();
-  if (timing) {
-    double sx = 0, sr = 0;
-    for (int L = 0; L < T; L++) {
-      float ms = 0;
-      HIPCHK(hipEventElapsedTime(&ms, kx[2 * L], kx[2 * L + 1]));
-      sx += ms;
-      HIPCHK(hipEventElapsedTime(&ms, kr[2 * L], kr[2 * L + 1]));
-      sr += ms;
-    }
-    out->ms_expand_kernels = sx;
-    out->ms_resolve_kernels = sr;
-    out->n_expand_launches = (uint64_t)T;
-    out->n_resolve_launches = (uint64_t)T;
-  }
-  for (auto e : ev) (void)hipEventDestroy(e);
-  out->positions = red[0];
-  out->edges = red[1];
-  out->primitives = red[2];
-  out->levels = (uint32_t)T;
-  out->max_level_width = 0;
-  out->word_bits = s0->wbits();
-  out->kernels = s0->rk | (s0->pk << 16);
-  for (gm_solver* s : ss)
-    if (s->launch_err) return fail(GM_ECORRUPT, "a level found no resolve kernel of the table's word width");
-  const uint32_t word = red[3] ? (uint32_t)(red[3] - 1) : NO_WORD;
-  out->root_word = word;
-  if (red[4]) return fail(GM_ECORRUPT, "solve failed:%s", err_text((uint32_t)red[4]).c_str());
-  if (word == NO_WORD) return fail(GM_ECORRUPT, "root unresolved");
-  out->root_value = (int32_t)(word & 3u);
-  out->root_remoteness = word >> 2;
-  return 0;
-}
-
-static int solve_dense(gm_solver* s, gm_result* out) { return run_dense({s}, out); }
-
-// ---------------------------------------------------------------------------
-// BUCKETED solve (gm_bucketed.h).  Steps as in the other layouts: forward
-// step L (L < T - 1) builds level L + 1 from level L; backward step
-// 2T - 1 - L resolves level L.  The host reads back two small arrays per
-// forward level (partition sizes, then the level's unique count) to size
-// the next launches and check capacities BEFORE any kernel writes past
-// them; the backward pass is enqueued without host round trips.
-// ---------------------------------------------------------------------------
-static uint32_t bitlen64(u64 x) { return x ? 64u - (uint32_t)__builtin_clzll(x) : 0u; }
-// parent-range geometry of a level of n positions (B3-B5): coarse ranges
-// index >> pshift (< 256 of them), fine ranges index >> fb (<= 2^13 parents,
-// <= 256 per coarse range)
-static bool bk_ranges(u64 n, uint32_t* pshift, uint32_t* fb) {
-  const uint32_t bl = bitlen64(n ? n - 1 : 0);
-  *pshift = bl > 8 ? bl - 8 : 0;
-  *fb = std::min<uint32_t>(*pshift, (uint32_t)kBkRangeBits);
-  return *pshift - *fb <= (uint32_t)kBkMaxFineBits;
-}
-}  // extern "C"
-// the bucketed kernels' instantiation for a descriptor (fixed_kind: the
-// compile-time toot boards where one exists)
-template <class Fn>
-static void bk_dispatch(const Desc& d, Fn&& fn) {
-  switch (fixed_kind(d)) {
-    case K_TTT: fn(std::integral_constant<int, K_TTT>{}); break;
-    case K_TOOT_6x4: fn(std::integral_constant<int, K_TOOT_6x4>{}); break;
-    case K_TOOT_5x4: fn(std::integral_constant<int, K_TOOT_5x4>{}); break;
-    case K_TOOT_4x4: fn(std::integral_constant<int, K_TOOT_4x4>{}); break;
-    case K_TOOT: fn(std::integral_constant<int, K_TOOT>{}); break;
-    default: fn(std::integral_constant<int, K_OTHELLO>{}); break;
-  }
-}
-extern "C" {
-#define BK_KIND_LAUNCH(KERNEL, GRID, BLOCK, S, ...)                                                      \
-  bk_dispatch((S)->d, [&](auto kind_) {                                                                  \
-    constexpr int K_ = decltype(kind_)::value;                                                           \
-    hipLaunchKernelGGL(KERNEL<K_>, dim3(GRID), dim3(BLOCK), 0, (S)->stream, __VA_ARGS__);               \
-  })
-
-// parents per expand round for a mean branching avg: the round's children
-// should fill about 3/4 of the 8192-record stage (whole waves, 256..4096)
-static uint32_t bk_ppr(double avg) {
-  const double p = 0.75 * kBkExpandCap / std::max(avg, 0.25);
-  return (uint32_t)std::min<double>(4.0 * kBkExpandThreads, std::max<double>(256.0, std::floor(p / 64.0) * 64.0));
-}
-
-static int solve_bucketed(gm_solver* s, gm_result* out) {
-  const Desc& d = s->d;
-  const int T = d.max_levels;
-  const int first = (int)s->step_first, stop = s->step_stop ? (int)s->step_stop : 2 * T;
-  s->step_first = s->step_stop = 0;
-  const bool timing = (s->flags & GM_F_KERNEL_TIMING) && first == 0 && stop == 2 * T;
-  hipStream_t st = s->stream;
-  std::vector<hipEvent_t> ev;
-  auto new_event = [&](hipEvent_t* e) -> int {
-    HIPCHK(hipEventCreate(e));
-    ev.push_back(*e);
-    return 0;
-  };
-  auto cleanup = [&]() {
-    for (auto e : ev) (void)hipEventDestroy(e);
-    ev.clear();
-  };
-  hipEvent_t e0, e1, e2;
-  if (new_event(&e0) || new_event(&e1) || new_event(&e2)) return GM_EHIP;
-  // kernel-time spans (timing): [start, stop, forward?]
-  struct Span {
-    hipEvent_t a, b;
-    bool fwd;
-  };
-  std::vector<Span> spans;
-  u64 nfwd = 0, nbwd = 0;
-  auto span = [&](bool fwd) -> hipEvent_t* {  // opens a span; returns its stop event to record later
-    if (!timing) return nullptr;
-    Span x{};
-    x.fwd = fwd;
-    if (new_event(&x.a) || new_event(&x.b)) return nullptr;
-    if (hipEventRecord(x.a, st) != hipSuccess) return nullptr;
-    spans.push_back(x);
-    return &spans.back().b;
-  };
-  auto span_end = [&](hipEvent_t* b) -> int {
-    if (b) HIPCHK(hipEventRecord(*b, st));
-    return 0;
-  };
-  int rc = 0;
-  auto bail = [&](int code) {
-    (void)hipStreamSynchronize(st);
-    cleanup();
-    return code;
-  };
-  auto t0 = std::chrono::steady_clock::now();
-  HIPCHK(hipEventRecord(e0, st));
-  std::vector<BkLevel>& lv = s->lvh;
-  if (first == 0) {
-    HIPCHK(hipMemsetAsync(s->st, 0, devstate_bytes(T), st));
-    HIPCHK(hipMemsetAsync(s->bkL, 0, sizeof(BkLevel) * (size_t)T, st));
-    lv.assign((size_t)T, BkLevel{});
-    lv[0].n = 1;
-    HIPCHK(hipMemcpyAsync(s->bkK, &s->d.root, sizeof(u64), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(s->bkL, lv.data(), sizeof(BkLevel), hipMemcpyHostToDevice, st));
-  } else {
-    lv.assign((size_t)T, BkLevel{});
-    HIPCHK(hipMemcpyAsync(lv.data(), s->bkL, sizeof(BkLevel) * (size_t)T, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  std::vector<uint32_t> htot(2 * kBkC);
-  std::vector<std::vector<uint32_t>> keep;  // host arrays of async H2D copies, alive until the end
-  uint32_t herr = 0;
-  // ---- forward ----
-  for (int L = first; L < T && L < stop; L++) {
-    if (L + 1 >= T) continue;  // the last level expands nothing (backward checks it holds only primitives)
-    BkLevel& P = lv[(size_t)L];
-    BkLevel& X = lv[(size_t)L + 1];
-    u64 re_used = P.rb + P.ein;
-    u64 meta_used = 0;  // end of the meta tables of the levels so far
-    for (int i = 0; i <= L; i++) {
-      const BkLevel& Q = lv[(size_t)i];
-      if (Q.nbits) meta_used = std::max<u64>(meta_used, Q.cst_off + 2 * ((1ull << Q.nbits) + 1));
-      if (i < L && Q.eout) meta_used = std::max<u64>(meta_used, Q.rfo_off + ((Q.n + (1ull << Q.fb) - 1) >> Q.fb) + 1);
-    }
-    X = BkLevel{};
-    X.lb = P.lb + P.n;
-    X.rb = re_used;
-    if (!bk_ranges(P.n, &P.pshift, &P.fb))
-      return bail(fail(GM_ELIMIT, "level %d holds %llu positions: more than the 2^29 a bucketed level supports", L,
-                       (unsigned long long)P.n));
-    P.eout = 0;
-    if (P.n) {
-      const u64 nblk = std::min<u64>(kBkExpandBlocks, (P.n + kBkExpandThreads - 1) / kBkExpandThreads),
-                chunk = (P.n + nblk - 1) / nblk;
-      const uint32_t NR = (uint32_t)((P.n + (1ull << P.fb) - 1) >> P.fb);
-      if (meta_used + NR + 1 > s->meta_cap) return bail(fail(GM_ECORRUPT, "bucket tables exceed the scratch"));
-      P.rfo_off = (uint32_t)meta_used;
-      meta_used += NR + 1;
-      uint32_t* rfo = s->meta + P.rfo_off;  // answers per fine parent range -> their starts
-      keep.emplace_back(2 * (kBkC + 1));
-      std::vector<uint32_t>& hb = keep.back();  // [coarse bases | parent-range bases]
-      u64 E = 0, Ep = 0;
-      // Count-free form first (k_bk_expand<OVER>): children go straight to
-      // provisioned partitions; a partition past its share -> the exact
-      // form (F0 counts, then k_bk_expand<false>) for this level.
-      // a partition's provisioned share, whole chunks of the chunked staging
-      uint32_t ck_sh = 14;
-      while (ck_sh > 6 && (s->Emax / kBkC) < (1ull << ck_sh)) ck_sh--;
-      const uint32_t cap = (uint32_t)((s->Emax / kBkC) >> ck_sh << ck_sh);
-      const BkChunked ck{(char*)s->S1k, ck_sh};
-      uint32_t incap = 0;
-      bool exact = true;
-      hipEvent_t* sp = nullptr;
-      if (!(s->flags & GM_F_BK_EXACT)) {
-        HIPCHK(hipMemsetAsync(rfo, 0, (NR + 1) * 4, st));
-        HIPCHK(hipMemsetAsync(s->bkgc, 0, (2 * kBkC + 4) * 4, st));
-        // parents per round from the previous level's branching (a round's
-        // children should fill most of the 8192-record stage)
-        const double avg = (L > 0 && lv[(size_t)L - 1].n) ? std::max(1.0, (double)P.ein / (double)lv[(size_t)L - 1].n) : 4.0;
-        const uint32_t ppr = bk_ppr(avg);
-        sp = span(true);
-        bk_dispatch(s->d, [&](auto kind_) {
-          constexpr int K_ = decltype(kind_)::value;
-          hipLaunchKernelGGL((k_bk_expand<K_, true>), dim3(nblk), dim3(kBkExpandThreads), 0, st, s->d, s->bkK + P.lb, P.n,
-                             chunk, (const uint32_t*)nullptr, (const uint32_t*)nullptr, ppr, s->S1k, s->S1p, s->S1f, cap,
-                             s->bkgc, P.pshift, P.fb, s->bkgc + kBkC, rfo, s->bkgc + 2 * kBkC, s->st, ck);
-        });
-        hipLaunchKernelGGL(k_bk_scan, dim3(1), dim3(1024), 0, st, rfo, NR + 1, rfo, s->bktotal + 1);
-        if ((rc = span_end(sp))) return bail(rc);
-        nfwd += 2;
-        HIPCHK(hipGetLastError());
-        std::vector<uint32_t> g(2 * kBkC + 1);
-        HIPCHK(hipMemcpyAsync(g.data(), s->bkgc, g.size() * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(&herr, &s->st->err, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (herr) return bail(fail(GM_ECORRUPT, "level %d:%s", L, err_text(herr).c_str()));
-        if (!g[2 * kBkC]) {
-          exact = false;
-          incap = cap;
-          for (int j = 0; j < kBkC; j++) {
-            hb[(size_t)j] = (uint32_t)E;
-            hb[(size_t)kBkC + 1 + j] = (uint32_t)Ep;
-            E += g[(size_t)j];
-            Ep += g[(size_t)kBkC + j];
-          }
-        }
-      }
-      if (exact) {
-        HIPCHK(hipMemsetAsync(rfo, 0, (NR + 1) * 4, st));
-        sp = span(true);
-        BK_KIND_LAUNCH(k_bk_count, nblk, kBkStreamThreads, s, s->d, s->bkK + P.lb, P.n, chunk, P.pshift, P.fb, s->bh,
-                       s->ph, rfo, s->st);
-        hipLaunchKernelGGL(k_bk_colscan, dim3(kBkC), dim3(256), 0, st, s->bh, (uint32_t)nblk, s->boff, s->tot);
-        hipLaunchKernelGGL(k_bk_colscan, dim3(kBkC), dim3(256), 0, st, s->ph, (uint32_t)nblk, s->ph, s->tot + kBkC);
-        hipLaunchKernelGGL(k_bk_scan, dim3(1), dim3(1024), 0, st, rfo, NR + 1, rfo, s->bktotal + 1);
-        if ((rc = span_end(sp))) return bail(rc);
-        nfwd += 4;
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(htot.data(), s->tot, 2 * kBkC * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(&herr, &s->st->err, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (herr) return bail(fail(GM_ECORRUPT, "level %d:%s", L, err_text(herr).c_str()));
-        for (int j = 0; j < kBkC; j++) {
-          hb[(size_t)j] = (uint32_t)E;
-          hb[(size_t)kBkC + 1 + j] = (uint32_t)Ep;
-          E += htot[(size_t)j];
-          Ep += htot[(size_t)kBkC + j];
-        }
-      }
-      if (E != Ep) return bail(fail(GM_ECORRUPT, "level %d: %llu children by partition, %llu by parent", L,
-                                    (unsigned long long)E, (unsigned long long)Ep));
-      if (E > s->Emax) return bail(fail(GM_EFULL, "level %d emits %llu children; the plan holds %llu per level", L,
-                                        (unsigned long long)E, (unsigned long long)s->Emax));
-      if (re_used + E > s->Ecap) return bail(fail(GM_EFULL, "edges exceed the plan's %llu", (unsigned long long)s->Ecap));
-      hb[(size_t)kBkC] = (uint32_t)E;
-      hb[(size_t)2 * kBkC + 1] = (uint32_t)Ep;
-      P.eout = E;
-      X.ein = E;
-      HIPCHK(hipMemcpyAsync(s->cbase, hb.data(), (kBkC + 1) * 4, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(s->pbase + (size_t)L * (kBkC + 1), hb.data() + kBkC + 1, (kBkC + 1) * 4,
-                            hipMemcpyHostToDevice, st));
-      if (E) {
-        uint32_t f = 0;
-        while (f < (uint32_t)kBkMaxFineBits && (E >> f) > (u64)kBkC * 4096) f++;
-        const uint32_t F = 1u << f, NB = (uint32_t)kBkC << f;
-        X.nbits = 8 + f;
-        if (meta_used + 2 * (NB + 1) > s->meta_cap) return bail(fail(GM_ECORRUPT, "bucket tables exceed the scratch"));
-        X.cst_off = (uint32_t)meta_used;
-        uint32_t* cst = s->meta + X.cst_off;
-        uint32_t* fo = cst + NB + 1;  // kept: the backward pass walks the level's in-edges bucket by bucket
-        const int gd = (int)std::min<uint32_t>(NB, 512);  // two workgroups per CU
-        sp = span(true);
-        if (exact) {  // parents per expand round: about a stage (8192 records) of children
-          const double avg = (double)E / (double)P.n;
-          const uint32_t ppr = bk_ppr(avg);
-          bk_dispatch(s->d, [&](auto kind_) {
-            constexpr int K_ = decltype(kind_)::value;
-            hipLaunchKernelGGL((k_bk_expand<K_, false>), dim3(nblk), dim3(kBkExpandThreads), 0, st, s->d, s->bkK + P.lb,
-                               P.n, chunk, (const uint32_t*)s->boff, (const uint32_t*)s->cbase, ppr, s->S1k, s->S1p,
-                               s->S1f, 0u, (uint32_t*)nullptr, 0u, 0u, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                               (uint32_t*)nullptr, s->st, BkChunked{nullptr, 0});
-          });
-          nfwd++;
-        }
-        // the fine partition writes the parents straight into the level's
-        // in-edge parents (REp); F3 adds the child indices (REc)
-        hipLaunchKernelGGL(k_bk_fine, dim3(kBkC), dim3(kBkFineThreads), 0, st, (const u64*)s->S1k,
-                           (const uint32_t*)s->S1p, (const uint8_t*)s->S1f, (const uint32_t*)s->cbase, 8u - f, F, s->S2k,
-                           s->REp + X.rb, fo, P.pshift, s->bkah + (size_t)L * kBkC * kBkC, incap, ck);
-        // unique keys of bucket b to S1k[fo[b] ..), compacted into the level
-        hipLaunchKernelGGL(k_bk_dedup, dim3(gd), dim3(kBkDedupThreads), 0, st, s->S2k, (const uint32_t*)fo, NB, s->S1k,
-                           s->ucnt, s->REc + X.rb, s->st);
-        hipLaunchKernelGGL(k_bk_scan, dim3(1), dim3(1024), 0, st, s->ucnt, NB, cst, s->bktotal);
-        if ((rc = span_end(sp))) return bail(rc);
-        nfwd += 3;
-        HIPCHK(hipGetLastError());
-        u64 n1 = 0;
-        HIPCHK(hipMemcpyAsync(&n1, s->bktotal, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(&herr, &s->st->err, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (herr) {
-          // a fine bucket over kBkMaxUnique keys follows from the level's
-          // real edges, not from the buffers: more memory cannot fix it
-          const bool lim = herr & ERR_BUCKET_FULL;
-          return bail(fail(lim ? GM_ELIMIT : GM_ECORRUPT, "level %d:%s", L + 1, err_text(herr).c_str()));
-        }
-        if (X.lb + n1 > s->Pcap) return bail(fail(GM_EFULL, "positions exceed the plan's %llu", (unsigned long long)s->Pcap));
-        X.n = n1;
-        sp = span(true);
-        hipLaunchKernelGGL(k_bk_compact, dim3(std::min<uint32_t>(NB, 4096)), dim3(256), 0, st, (const u64*)s->S1k,
-                           (const uint32_t*)fo, (const uint32_t*)cst, NB, s->bkK + X.lb);
-        if ((rc = span_end(sp))) return bail(rc);
-        nfwd++;
-        HIPCHK(hipGetLastError());
-      }
-    }
-    HIPCHK(hipMemcpyAsync(s->bkL + L, &lv[(size_t)L], 2 * sizeof(BkLevel), hipMemcpyHostToDevice, st));
-  }
-  HIPCHK(hipEventRecord(e1, st));
-  // ---- backward ----
-  for (int L = T - 1; L >= 0; L--) {
-    const int k = 2 * T - 1 - L;
-    if (k < first) continue;
-    if (k >= stop) break;
-    BkLevel& P = lv[(size_t)L];
-    if (!P.n) continue;
-    if (!bk_ranges(P.n, &P.pshift, &P.fb)) return bail(fail(GM_ELIMIT, "level %d too wide for bucketed levels", L));
-    const uint32_t NR = (uint32_t)((P.n + (1ull << P.fb) - 1) >> P.fb);
-    const int gr = (int)std::min<uint32_t>(NR, 512);
-    hipEvent_t* sp = span(false);
-    if (L + 1 < T && P.eout) {
-      const BkLevel& X = lv[(size_t)L + 1];
-      const uint32_t NB = 1u << X.nbits, F = NB / kBkC;
-      const uint32_t* cst = s->meta + X.cst_off;
-      const uint32_t* fo = cst + NB + 1;
-      const uint32_t* rfo = s->meta + P.rfo_off;
-      const uint32_t* pb = s->pbase + (size_t)L * (kBkC + 1);
-      uint32_t* Ap = (uint32_t*)s->S1k;
-      constexpr uint32_t K = kBkSplitK;  // B4 workgroups per range
-      // B3: one workgroup per children's partition, exact offsets per
-      // (partition, parent range) from the counts F2 kept (ah).  (Measured:
-      // K = 4 workgroups of 512 threads per partition on device run cursors
-      // took 50.5 ms of backward against 48.2 for this form.)
-      hipLaunchKernelGGL(k_bk_colscan, dim3(kBkC), dim3(256), 0, st, s->bkah + (size_t)L * kBkC * kBkC, (uint32_t)kBkC,
-                         s->boff, s->tot);
-      hipLaunchKernelGGL(k_bk_answer, dim3(kBkC), dim3(kBkStreamThreads), 0, st, s->REp + X.rb, s->REc + X.rb, fo, cst,
-                         NB, F, P.pshift, s->boff, pb, s->bkW + X.lb, Ap, s->st);
-      nbwd += 2;
-      const uint32_t Fp = 1u << (P.pshift - P.fb);
-      const uint32_t* ap = Ap;
-      if (Fp > 1) {
-        HIPCHK(hipMemcpyAsync(s->bkcur + kBkC, rfo, (size_t)NR * 4, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(k_bk_split, dim3(kBkC * K), dim3(kBkStreamThreads), 0, st, (const uint32_t*)Ap, pb,
-                           10u + P.fb, Fp, K, s->bkcur + kBkC, (uint32_t*)s->S2k);
-        ap = (uint32_t*)s->S2k;
-        nbwd++;
-      }
-      BK_KIND_LAUNCH(k_bk_reduce, gr, kBkReduceThreads, s, s->d, s->bkK + P.lb, P.n, ap, rfo, P.fb, Fp - 1, NR,
-                     s->bkW + P.lb, s->st);
-    } else {
-      BK_KIND_LAUNCH(k_bk_reduce, gr, kBkReduceThreads, s, s->d, s->bkK + P.lb, P.n, (const uint32_t*)nullptr,
-                     (const uint32_t*)nullptr, P.fb, 0u, NR, s->bkW + P.lb, s->st);
-    }
-    nbwd++;
-    if ((rc = span_end(sp))) return bail(rc);
-    HIPCHK(hipGetLastError());
-  }
-  HIPCHK(hipEventRecord(e2, st));
-  if (stop < 2 * T) {  // stopped early: the state stays in the buffers for a resume
-    HIPCHK(hipMemcpyAsync(s->bkL, lv.data(), sizeof(BkLevel) * (size_t)T, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-    cleanup();
-    out->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return GM_PARTIAL;
-  }
-  HIPCHK(hipMemcpyAsync(s->bkL, lv.data(), sizeof(BkLevel) * (size_t)T, hipMemcpyHostToDevice, st));
-  uint32_t root_word = NO_WORD;
-  HIPCHK(hipMemcpyAsync(&root_word, s->bkW, 4, hipMemcpyDeviceToHost, st));
-  std::vector<unsigned char> host(devstate_bytes(T));
-  HIPCHK(hipMemcpyAsync(host.data(), s->st, host.size(), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  auto t1 = std::chrono::steady_clock::now();
-  const DevState* hs = (const DevState*)host.data();
-  float f = 0, b = 0;
-  HIPCHK(hipEventElapsedTime(&f, e0, e1));
-  HIPCHK(hipEventElapsedTime(&b, e1, e2));
-  out->ms_forward = f;
-  out->ms_backward = b;
-  out->ms_total = std::chrono::duration<double, std::milli>(t1 - t0).count();
-  if (timing) {
-    double sx = 0, sr = 0;
-    for (const Span& x : spans) {
-      float ms = 0;
-      HIPCHK(hipEventElapsedTime(&ms, x.a, x.b));
-      (x.fwd ? sx : sr) += ms;
-    }
-    out->ms_expand_kernels = sx;
-    out->ms_resolve_kernels = sr;
-    out->n_expand_launches = nfwd;
-    out->n_resolve_launches = nbwd;
-  }
-  cleanup();
-  u64 pos = 0, wmax = 0;
-  uint32_t nlev = 0;
-  for (const BkLevel& x : lv) {
-    pos += x.n;
-    wmax = std::max<u64>(wmax, x.n);
-    nlev += x.n > 0;
-  }
-  out->positions = pos;
-  out->edges = hs->edges;
-  out->primitives = hs->prims;
-  out->levels = nlev;
-  out->max_level_width = (uint32_t)std::min<u64>(wmax, 0xFFFFFFFFull);
-  out->root_word = root_word;
-  if (hs->err) {
-    const bool full = hs->err & (ERR_TABLE_FULL | ERR_LEVELS_FULL);
-    const bool lim = hs->err & ERR_BUCKET_FULL;
-    return fail(lim ? GM_ELIMIT : full ? GM_EFULL : GM_ECORRUPT, "solve failed:%s", err_text(hs->err).c_str());
-  }
-  if (root_word == NO_WORD) return fail(GM_ECORRUPT, "root unresolved");
-  out->root_value = (int32_t)(root_word & 3u);
-  out->root_remoteness = root_word >> 2;
-  return 0;
-}
-
-#include "gm_bucketed_shard.h"
 
 int gm_solve_group(gm_solver** shards, int n, gm_result* out) {
   if (!shards || n < 1 || !out) return fail(GM_EINVAL, "bad argument");
@@ -3815,14 +1983,16 @@ int gm_solve_group(gm_solver** shards, int n, gm_result* out) {
   for (gm_solver* s : ss)
     if (!s) return fail(GM_EINVAL, "null shard");
   for (gm_solver* s : ss) s->solved = false;
-  int rc;
-  if (ss[0]->mode == GM_MODE_PLANES) rc = run_planes(ss, out);
-  else if (ss[0]->mode == GM_MODE_BUCKETED) rc = run_bucketed_shards(ss, out);
-  else if (ss[0]->mode == GM_MODE_RANKED) rc = ss[0]->world > 1 ? run_ranked_shards(ss, out) : run_ranked(ss[0], out);
-  else rc = run_dense(ss, out);
+  // a group's BUCKETED shards take the sharded loop whatever their world, and
+  // keyed tables meet the dense loop's group checks; the rest is one dispatch
+  const uint32_t mode = ss[0]->mode;
+  const int rc = mode == GM_MODE_BUCKETED ? run_bucketed_shards(ss, out)
+                 : mode == GM_MODE_HASHED ? run_dense(ss, out)
+                                          : solve_by_mode(ss, out);
   for (gm_solver* s : ss) s->solved = rc == 0;
   return rc;
 }
+
 
 #include "gm_moves.h"
 

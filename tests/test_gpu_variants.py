@@ -130,6 +130,79 @@ def test_shard_geometries_like_the_bench(world, params):
     np.testing.assert_array_equal(out >> 2, rem)
 
 
+SMALL = "heaps=15:15:15:15:7"  # one table, 8-bit words, live-group lists, tail runs
+
+
+def _small(**kw):
+    """A dense solver of SMALL, its first solve's result and its sorted table."""
+    from gamesmanmpi_amd.games import GameSpec
+    from gamesmanmpi_amd.solver import Solver
+    s = Solver(GameSpec("sum_four_to_one", SMALL), layout="dense", **kw)
+    r = s.solve()
+    return s, r, _table(s)
+
+
+def _table(s):
+    keys, val, rem = s.dump()
+    order = np.argsort(keys)
+    return keys[order], val[order], rem[order]
+
+
+@pytest.fixture(scope="module")
+def small_plain():
+    _, r, table = _small()
+    assert r.extra["word_bits"] == 8 and r.extra["resolve_kernel"] == "k_dense_resolve16p", r.extra
+    return r, table
+
+
+def _same_solve(r, table, plain):
+    r0, table0 = plain
+    assert (r.positions, r.edges, r.root_line) == (r0.positions, r0.edges, r0.root_line)
+    for got, want in zip(table, table0):
+        np.testing.assert_array_equal(got, want)
+
+
+def test_graph_capture_and_replay_equal_the_plain_solve(small_plain):
+    """GM_F_GRAPH: the first solve captures the two passes and replays them,
+    the second only replays; both leave the plain solve's table."""
+    from gamesmanmpi_amd import _lib
+    s, r, table = _small(flags=_lib.GM_F_GRAPH)
+    _same_solve(r, table, small_plain)
+    _same_solve(s.solve(), _table(s), small_plain)
+
+
+def test_kernel_timing_times_one_launch_per_level(small_plain):
+    """GM_F_KERNEL_TIMING: the plain solve's words from one launch per level
+    and pass (no tail runs), each timed inside the passes' own spans."""
+    s, r, table = _small(kernel_timing=True)
+    _same_solve(r, table, small_plain)
+    T = int(s.plan.max_levels)
+    assert r.n_expand_launches == r.n_resolve_launches == T
+    for ms in (r.ms_expand_kernels, r.ms_resolve_kernels):
+        assert 0 < ms <= r.ms_forward + r.ms_backward, (ms, r.ms_forward, r.ms_backward)
+
+
+def test_a_refused_resume_leaves_the_solver_usable(small_plain):
+    """A resume (first step 1) on a solver that never solved is GM_EINVAL --
+    an early return taken after the solve's setup began -- and however often
+    it is refused the solver then solves correctly."""
+    from gamesmanmpi_amd import _lib
+    from gamesmanmpi_amd.games import GameSpec
+    from gamesmanmpi_amd.solver import Solver
+    L = _lib.load()
+    s = Solver(GameSpec("sum_four_to_one", SMALL), layout="dense")
+    # fresh: no solve in progress in the scratch's DevState, whatever the
+    # allocator left there (DevState::word_bits lies in its first 128 bytes)
+    s.buffers[2][:128].zero_()
+    s.torch.cuda.synchronize()
+    for _ in range(50):
+        _lib.check(L.gm_solver_set_steps(s.handle, 1, 0))
+        res = _lib.gm_result()
+        assert L.gm_solver_solve(s.handle, ctypes.byref(res)) == _lib.GM_EINVAL
+        assert b"resume" in L.gm_last_error()
+    assert s.solve().root_line == small_plain[0].root_line
+
+
 def test_16bit_table_refuses_32bit_kernels():
     """The round-1 fault class (a 32-bit kernel writing past a 16-bit word
     area): kernel families are fixed at creation from the flags the table

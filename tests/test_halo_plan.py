@@ -4,6 +4,9 @@ neighbour posts to receive -- bits go down, words go up (DESIGN.md
 §Multi-GPU; the check gm_solver_solve runs over RCCL / the host transport
 before level 0 and turns into GM_ECORRUPT instead of a hung receive).
 Covers the bench's 2^30 shape at N = 2, 4, 8 and the test shapes."""
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -34,6 +37,22 @@ def test_bench_shape_plans_pair(world):
                                           ("heaps=15:15:15:15:127", 8), ("heaps=7:7:7:7:7", 2)])
 def test_test_shape_plans_pair(params, world):
     _pairs_match(GameSpec("sum_four_to_one", params), world)
+
+
+@pytest.mark.parametrize("params,world", [("heaps=7:7:7:7:7", 2), ("heaps=15:15:15:15:31", 3)])
+def test_signatures_match_the_recorded_ones(params, world):
+    """Every rank's signatures equal the ones recorded in tests/golden/
+    halo_sigs.json (from the build before the solver's setup and
+    gm_shard_halo_sigs shared one host geometry, dense_host_geom): a drift in
+    that geometry -- which the pairing above cannot see when both ends
+    drift alike -- fails here, without a GPU."""
+    with open(os.path.join(os.path.dirname(__file__), "golden", "halo_sigs.json")) as f:
+        want = json.load(f)["sigs"]["%s world=%d" % (params, world)]
+    spec = GameSpec("sum_four_to_one", params)
+    assert len(want) == world
+    for r in range(world):
+        got = ["%016x" % int(x) for x in halo_sigs(spec, r, world).reshape(-1)]
+        assert got == want[r], "rank %d" % r
 
 
 def test_a_wrong_geometry_is_detected():
