@@ -211,127 +211,32 @@ __global__ void k_bks_wu(const u64* __restrict__ in, u64 n, uint32_t* Wu) {
 // host
 // ---------------------------------------------------------------------------
 // One all-to-all of eb-byte elements: shard r sends sbuf[so[p] ..) (sc[p]
-// elements) to p and receives rbuf[ro[p] ..) (rc[p]) from p.  mode 1 RCCL,
-// 2 in-process copies (every shard in ss), 3 host-staged transport, 4 the
-// rehearsal of mode 1 (every shard in ss, each on its own stream).
+// elements) to p and receives rbuf[ro[p] ..) (rc[p]) from p, its own share
+// included (a[g]: shard ss[g]'s; the transports: gm_xchg.h)
 struct BksA2A {
   char* sbuf;
   char* rbuf;
   std::vector<u64> sc, so, rc, ro;
 };
-static int bks_alltoall(std::vector<gm_solver*>& ss, int mode, hipStream_t st, std::vector<BksA2A>& a, u64 eb) {
+static int bks_alltoall(std::vector<gm_solver*>& ss, Xchg mode, hipStream_t st, std::vector<BksA2A>& a, u64 eb) {
   const int W = ss[0]->world;
-  if (mode == 4) {
-    // RCCL's grouped send / receive on each rank's own stream (mode 1),
-    // rehearsed with the shards on streams of their own: every sender's
-    // records are final on its stream (ready[r]); each receiver's stream
-    // waits for every sender and copies its incoming segments; every
-    // stream then waits for every receiver (done[p]) -- a send completes
-    // only with the transfer, so no rank reuses its buffers early
-    for (gm_solver* s : ss)
-      while (s->pev.size() < 2) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        s->pev.push_back(e);
-      }
-    for (gm_solver* s : ss) HIPCHK(hipEventRecord(s->pev[0], s->stream));
+  std::vector<XLists> x(ss.size());
+  for (size_t g = 0; g < ss.size(); g++)
     for (int p = 0; p < W; p++) {
-      gm_solver* t = ss[(size_t)p];
-      for (int r = 0; r < W; r++) {
-        const u64 n = a[(size_t)r].sc[(size_t)p];
-        if (n != a[(size_t)p].rc[(size_t)r])
-          return fail(GM_ECORRUPT, "exchange: shard %d sends %llu to %d, which expects %llu", r, (unsigned long long)n,
-                      p, (unsigned long long)a[(size_t)p].rc[(size_t)r]);
-        if (!n) continue;
-        if (r != p) HIPCHK(hipStreamWaitEvent(t->stream, ss[(size_t)r]->pev[0], 0));
-        HIPCHK(hipMemcpyAsync(a[(size_t)p].rbuf + a[(size_t)p].ro[(size_t)r] * eb,
-                              a[(size_t)r].sbuf + a[(size_t)r].so[(size_t)p] * eb, n * eb, hipMemcpyDeviceToDevice,
-                              t->stream));
-      }
-      HIPCHK(hipEventRecord(t->pev[1], t->stream));
+      x[g].out.push_back({p, a[g].sbuf + a[g].so[(size_t)p] * eb, a[g].sc[(size_t)p] * eb});
+      x[g].in.push_back({p, a[g].rbuf + a[g].ro[(size_t)p] * eb, a[g].rc[(size_t)p] * eb});
     }
-    for (gm_solver* s : ss)
-      for (gm_solver* t : ss)
-        if (t != s) HIPCHK(hipStreamWaitEvent(s->stream, t->pev[1], 0));
-    return 0;
-  }
-  if (mode == 2) {
-    for (int r = 0; r < W; r++)
-      for (int p = 0; p < W; p++) {
-        const u64 n = a[(size_t)r].sc[(size_t)p];
-        if (n != a[(size_t)p].rc[(size_t)r])
-          return fail(GM_ECORRUPT, "exchange: shard %d sends %llu to %d, which expects %llu", r, (unsigned long long)n,
-                      p, (unsigned long long)a[(size_t)p].rc[(size_t)r]);
-        if (n)
-          HIPCHK(hipMemcpyAsync(a[(size_t)p].rbuf + a[(size_t)p].ro[(size_t)r] * eb,
-                                a[(size_t)r].sbuf + a[(size_t)r].so[(size_t)p] * eb, n * eb, hipMemcpyDeviceToDevice, st));
-      }
-    return 0;
-  }
-  gm_solver* s = ss[0];
-  BksA2A& x = a[0];
-  const int r = s->rank;
-  if (x.sc[(size_t)r] != x.rc[(size_t)r]) return fail(GM_ECORRUPT, "exchange: self counts differ");
-  if (x.sc[(size_t)r])
-    HIPCHK(hipMemcpyAsync(x.rbuf + x.ro[(size_t)r] * eb, x.sbuf + x.so[(size_t)r] * eb, x.sc[(size_t)r] * eb,
-                          hipMemcpyDeviceToDevice, st));
-  if (mode == 1) {
-    RCCL_LIVE(s);
-    ncclGroupStart();
-    ncclResult_t e1 = ncclSuccess, e2 = ncclSuccess;
-    for (int p = 0; p < W; p++) {
-      if (p == r) continue;
-      if (x.sc[(size_t)p] && e1 == ncclSuccess)
-        e1 = ncclSend(x.sbuf + x.so[(size_t)p] * eb, x.sc[(size_t)p] * eb, ncclUint8, p, s->comm, st);
-      if (x.rc[(size_t)p] && e2 == ncclSuccess)
-        e2 = ncclRecv(x.rbuf + x.ro[(size_t)p] * eb, x.rc[(size_t)p] * eb, ncclUint8, p, s->comm, st);
-    }
-    const ncclResult_t e3 = ncclGroupEnd();
-    if (e1 != ncclSuccess || e2 != ncclSuccess || e3 != ncclSuccess)
-      return fail(GM_EHIP, "RCCL all-to-all: %s",
-                  ncclGetErrorString(e1 != ncclSuccess ? e1 : e2 != ncclSuccess ? e2 : e3));
-    return 0;
-  }
-  // host-staged: W - 1 rounds, round k pairs r -> r + k with r - k -> r
-  for (int k = 1; k < W; k++) {
-    const int to = (r + k) % W, from = (r - k + W) % W;
-    std::vector<HostRange> out, in;
-    if (x.sc[(size_t)to]) out.push_back({x.sbuf + x.so[(size_t)to] * eb, x.sc[(size_t)to] * eb});
-    if (x.rc[(size_t)from]) in.push_back({x.rbuf + x.ro[(size_t)from] * eb, x.rc[(size_t)from] * eb});
-    int rc = xfer_ranges(s, out, to, in, from, st);
-    if (rc) return rc;
-  }
-  return 0;
+  if (xchg_group(mode)) return xchg_copies(ss, mode, st, x);
+  return xchg_ranges(ss[0], mode, st, x[0], xchg_rounds(ss[0]->rank, W), "all-to-all");
 }
 
-// every shard's row of a W-wide u64 vector, all-gathered: out[r * W + p]
-static int bks_allgather(std::vector<gm_solver*>& ss, int mode, hipStream_t st, const std::vector<std::vector<u64>>& mine,
+// every shard's row of a u64 vector, all-gathered: out[r * m + i]
+static int bks_allgather(std::vector<gm_solver*>& ss, Xchg mode, hipStream_t st, const std::vector<std::vector<u64>>& mine,
                          std::vector<u64>& out) {
-  const int W = ss[0]->world;
-  const size_t m = mine[0].size();
-  out.assign((size_t)W * m, 0);
-  if (mode == 2 || mode == 4) {
-    for (int r = 0; r < W; r++) std::copy(mine[(size_t)r].begin(), mine[(size_t)r].end(), out.begin() + (size_t)r * m);
-    return 0;
-  }
-  gm_solver* s = ss[0];
-  if (mode == 3) return xfer_call(s, GM_XFER_ALLGATHER, mine[0].data(), m * 8, -1, out.data(), out.size() * 8, -1);
-  if (s->xdev_n < m + out.size()) {  // kept across levels and solves (freed with the solver)
-    if (s->xdev) (void)hipFree(s->xdev);
-    s->xdev = nullptr;
-    s->xdev_n = 0;
-    HIPCHK(hipMalloc((void**)&s->xdev, (m + out.size()) * 8));
-    s->xdev_n = m + out.size();
-  }
-  u64* dev = s->xdev;
-  RCCL_LIVE(s);
-  HIPCHK(hipMemcpyAsync(dev, mine[0].data(), m * 8, hipMemcpyHostToDevice, st));
-  const ncclResult_t r = ncclAllGather(dev, dev + m, m, ncclUint64, s->comm, st);
-  hipError_t e = hipMemcpyAsync(out.data(), dev + m, out.size() * 8, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (r != ncclSuccess) return fail(GM_EHIP, "RCCL all-gather: %s", ncclGetErrorString(r));
-  if (e != hipSuccess) return fail(GM_EHIP, "all-gather: %s", hipGetErrorString(e));
-  return 0;
+  return xchg_allgather(ss, mode, st, mine[0].size(), out, [&](gm_solver* s, u64* row) {
+    const std::vector<u64>& v = mine[xchg_group(mode) ? (size_t)s->rank : 0];
+    std::copy(v.begin(), v.end(), row);
+  });
 }
 
 static std::vector<u64> bks_prefix(const std::vector<u64>& c) {
@@ -347,22 +252,13 @@ static int run_bucketed_shards(std::vector<gm_solver*> ss, gm_result* out) {
   gm_solver* s0 = ss[0];
   const Desc& d = s0->d;
   const int T = d.max_levels, W = s0->world;
-  // mode 2: a group on one stream; mode 4: a group whose shards run on
-  // streams of their own -- mode 1's per-rank stream order, the all-to-alls
-  // as device copies between the shards' streams (bks_alltoall)
-  const bool own_streams = ss.size() > 1 && ss[1]->stream != s0->stream;
-  const int mode = ss.size() != 1 ? (own_streams ? 4 : 2) : s0->xfer ? 3 : 1;
-  if (mode == 1 && !s0->comm) return fail(GM_EINVAL, "shard %d/%d has no communicator (gm_solver_comm_init)", s0->rank, W);
-  if (mode == 2 || mode == 4) {
-    if ((int)ss.size() != W) return fail(GM_EINVAL, "group solve needs all %d shards", W);
-    for (size_t g = 0; g < ss.size(); g++) {
-      if (ss[g]->rank != (int)g || ss[g]->mode != GM_MODE_BUCKETED)
-        return fail(GM_EINVAL, "group shards must be ranks 0..n-1");
-      for (size_t h = 0; h < g; h++)
-        if ((mode == 2) != (ss[g]->stream == ss[h]->stream))
-          return fail(GM_EINVAL, "group shards share one stream, or (the RCCL rehearsal) each has its own");
-    }
-  }
+  // XCHG_STREAMS: a group whose shards run on streams of their own -- RCCL's
+  // per-rank stream order, the all-to-alls as device copies between the
+  // shards' streams
+  Xchg mode;
+  int mrc = xchg_mode(ss, GM_MODE_BUCKETED, &mode);
+  if (mrc) return mrc;
+  if (mode == XCHG_TABLE) return fail(GM_EINVAL, "the sharded bucketed loop needs a plan of two or more shards");
   if (s0->step_first || s0->step_stop) return fail(GM_EINVAL, "sharded bucketed solves run whole (no steps)");
   // Which form a level's children take: the local-dedup form pays an extra
   // host sync and a second dedup per level, won back where a shard expands
@@ -397,7 +293,7 @@ static int run_bucketed_shards(std::vector<gm_solver*> ss, gm_result* out) {
     return code;
   };
   HIPCHK(hipEventRecord(e0, st));
-  if (mode == 4) HIPCHK(sync_all());  // the shards' streams start after e0 (host order)
+  if (mode == XCHG_STREAMS) HIPCHK(sync_all());  // the shards' streams start after e0 (host order)
   // the root's owner seeds level 0
   const uint32_t root_owner = owner_host(d, d.root, (uint32_t)W);
   for (gm_solver* s : ss) {
@@ -954,7 +850,7 @@ static int run_bucketed_shards(std::vector<gm_solver*> ss, gm_result* out) {
     if (!rc) rc = status_of(MA, (size_t)W + 3);
     if (rc) return bail(rc);
   }
-  if (mode == 4) HIPCHK(sync_all());  // e1 after every shard's forward
+  if (mode == XCHG_STREAMS) HIPCHK(sync_all());  // e1 after every shard's forward
   HIPCHK(hipEventRecord(e1, st));
   // ---- backward ----
   for (int L = T - 1; L >= 0; L--) {
@@ -1062,7 +958,7 @@ static int run_bucketed_shards(std::vector<gm_solver*> ss, gm_result* out) {
       HIPCHK(hipGetLastError());
     }
   }
-  if (mode == 4) HIPCHK(sync_all());  // e2 after every shard's backward
+  if (mode == XCHG_STREAMS) HIPCHK(sync_all());  // e2 after every shard's backward
   HIPCHK(hipEventRecord(e2, st));
   // ---- totals: positions, edges, primitives, root word + 1, error bits, per-level sizes ----
   std::vector<std::vector<u64>> mine(ss.size(), std::vector<u64>(5 + (size_t)T, 0));

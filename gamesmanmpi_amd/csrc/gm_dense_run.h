@@ -3,8 +3,8 @@
 // exchanges of a shard group with their fail-fast plan check, the solve loop
 // (run_dense: one table, an in-process shard group, or one shard per process
 // over RCCL / a host-staged transport) and the plan.  No kernels.  Included
-// by gm_solver.hip after the solver object and k_fill_red; the transport
-// helpers here (xfer_call, xfer_ranges) serve the other layouts' shards too.
+// by gm_solver.hip after the solver object, k_fill_red and the shards'
+// exchange layer (gm_xchg.h).
 
 // (gm_solver.hip includes this inside its extern "C" block: templates need
 // C++ linkage)
@@ -540,8 +540,8 @@ static DenseView dense_band(const Desc& d, const DenseView& v, u64 L) {
 // the same order.  Only the part of a slice pair inside level L's band
 // travels: bits as whole 64-bit words, words packed to their non-hole slots
 // (power-of-two tables, k_halo_move) or as the band's 4-B run.  `cs` is the
-// stream the copies / RCCL calls run on.  mode: 1 = RCCL (one process per
-// GPU), 2 = in-process group (device-to-device copies).
+// stream the exchange runs on; each exchange lists its ranges once and hands
+// them to the transport of the solve's mode (gm_xchg.h).
 
 // prefixes [lo, hi) (offsets inside the slice pair starting at top value
 // t0) of level L's band; false if none
@@ -557,116 +557,45 @@ static bool band_pair(const gm_solver* s, u64 L, int64_t t0, u64* lo, u64* hi) {
   return true;
 }
 
-static int xfer_call(gm_solver* s, int op, const void* sb, u64 sn, int sp, void* rb, u64 rn, int rp) {
-  const int rc = s->xfer(s->xfer_ctx, op, sb, sn, sp, rb, rn, rp);
-  return rc ? fail(GM_EHIP, "transport callback failed (%d) on rank %d", rc, s->rank) : 0;
-}
-// host-staged copy of device ranges into / out of s->hstage
-struct HostRange {
-  void* dev;
-  u64 bytes;
-};
-static int stage_out(gm_solver* s, const std::vector<HostRange>& rs, u64 at, hipStream_t cs) {
-  for (const HostRange& r : rs) {
-    HIPCHK(hipMemcpyAsync(s->hstage.data() + at, r.dev, r.bytes, hipMemcpyDeviceToHost, cs));
-    at += r.bytes;
-  }
-  HIPCHK(hipStreamSynchronize(cs));
-  return 0;
-}
-static int stage_in(gm_solver* s, const std::vector<HostRange>& rs, u64 at, hipStream_t cs) {
-  for (const HostRange& r : rs) {
-    HIPCHK(hipMemcpyAsync(r.dev, s->hstage.data() + at, r.bytes, hipMemcpyHostToDevice, cs));
-    at += r.bytes;
-  }
-  HIPCHK(hipStreamSynchronize(cs));
-  return 0;
-}
-static u64 ranges_bytes(const std::vector<HostRange>& rs) {
-  u64 n = 0;
-  for (const HostRange& r : rs) n += r.bytes;
-  return n;
-}
-// one paired transfer through the host: send ranges `out` to rank sp, receive
-// ranges `in` from rank rp
-static int xfer_ranges(gm_solver* s, const std::vector<HostRange>& out, int sp, const std::vector<HostRange>& in, int rp,
-                       hipStream_t cs) {
-  const u64 ns = ranges_bytes(out), nr = ranges_bytes(in);
-  if (s->hstage.size() < ns + nr) s->hstage.resize(ns + nr);
-  int rc = stage_out(s, out, 0, cs);
-  if (rc) return rc;
-  rc = xfer_call(s, GM_XFER_SENDRECV, s->hstage.data(), ns, sp, s->hstage.data() + ns, nr, rp);
-  if (rc) return rc;
-  return stage_in(s, in, ns, cs);
+// shard s's neighbour ranks
+static int ring_down(const gm_solver* s) { return (s->rank + s->world - 1) % s->world; }
+static int ring_up(const gm_solver* s) { return (s->rank + 1) % s->world; }
+// one halo exchange, up or down the ring, of the ranges x (x[g]: shard
+// ss[g]'s lists): a group's device copies, or this process's one shard over
+// its transport -- the host transport in ONE paired transfer
+static int exchange_ranges(std::vector<gm_solver*>& ss, Xchg mode, hipStream_t cs, const std::vector<XLists>& x, bool up,
+                           const char* what) {
+  if (xchg_group(mode)) return xchg_copies(ss, mode, cs, x);
+  gm_solver* s = ss[0];
+  const XRound ring = up ? XRound{ring_up(s), ring_down(s)} : XRound{ring_down(s), ring_up(s)};
+  return xchg_ranges(s, mode, cs, x[0], {ring}, what);
 }
 
-// after pull(L): bits of every block's bottom two own slices go down
-static int exchange_bits(std::vector<gm_solver*>& ss, u64 L, int mode, hipStream_t cs) {
+// after pull(L): bits of every block's bottom two own slices go down (to
+// block k-1, the upper halo there)
+static int exchange_bits(std::vector<gm_solver*>& ss, u64 L, Xchg mode, hipStream_t cs) {
   auto bits_at = [&](gm_solver* s, u64 j, u64 o, u64 off) {
     return s->bits + (L * s->view.Wbl + blk_slice(s, j, o) * s->view.Z + off) / 64;
   };
-  if (mode == 3) {  // host-staged: the same ranges, in the same order as the RCCL form
-    gm_solver* s = ss[0];
-    const int down = (s->rank + s->world - 1) % s->world, up = (s->rank + 1) % s->world;
+  std::vector<XLists> x(ss.size());
+  for (size_t g = 0; g < ss.size(); g++) {
+    gm_solver* s = ss[g];
     const u64 nb = blk_count(s), B = s->view.B;
-    std::vector<HostRange> out, in;
     for (u64 j = 0; j < nb; j++) {
       u64 lo, hi;
       if (blk_global(s, j) >= 1 && band_pair(s, L, blk_top(s, j, 2), &lo, &hi)) {
         lo &= ~63ull;
         hi = (hi + 63) & ~63ull;
-        out.push_back({bits_at(s, j, 2, lo), (hi - lo) / 8});
+        x[g].out.push_back({ring_down(s), bits_at(s, j, 2, lo), (hi - lo) / 8});
       }
       if (blk_global(s, j) + 1 < s->nblocks && band_pair(s, L, blk_top(s, j, B + 2), &lo, &hi)) {
         lo &= ~63ull;
         hi = (hi + 63) & ~63ull;
-        in.push_back({bits_at(s, j, B + 2, lo), (hi - lo) / 8});
+        x[g].in.push_back({ring_up(s), bits_at(s, j, B + 2, lo), (hi - lo) / 8});
       }
     }
-    return xfer_ranges(s, out, down, in, up, cs);
   }
-  if (mode == 1) {
-    gm_solver* s = ss[0];
-    const int down = (s->rank + s->world - 1) % s->world, up = (s->rank + 1) % s->world;
-    const u64 nb = blk_count(s), B = s->view.B;
-    RCCL_LIVE(s);
-    ncclGroupStart();
-    for (u64 j = 0; j < nb; j++) {
-      u64 lo, hi;
-      if (blk_global(s, j) >= 1 && band_pair(s, L, blk_top(s, j, 2), &lo, &hi)) {  // to block k-1
-        lo &= ~63ull;
-        hi = (hi + 63) & ~63ull;
-        ncclSend(bits_at(s, j, 2, lo), (hi - lo) / 8, ncclUint8, down, s->comm, cs);
-      }
-    }
-    for (u64 j = 0; j < nb; j++) {
-      u64 lo, hi;
-      if (blk_global(s, j) + 1 < s->nblocks && band_pair(s, L, blk_top(s, j, B + 2), &lo, &hi)) {  // from block k+1
-        lo &= ~63ull;
-        hi = (hi + 63) & ~63ull;
-        ncclRecv(bits_at(s, j, B + 2, lo), (hi - lo) / 8, ncclUint8, up, s->comm, cs);
-      }
-    }
-    ncclResult_t r = ncclGroupEnd();
-    if (r != ncclSuccess) return fail(GM_EHIP, "RCCL bits halo: %s", ncclGetErrorString(r));
-    return 0;
-  }
-  const int W = (int)ss.size();
-  for (gm_solver* s : ss) {
-    const u64 nb = blk_count(s), B = s->view.B;
-    for (u64 j = 0; j < nb; j++) {
-      const u64 k = blk_global(s, j);
-      u64 lo, hi;
-      if (k < 1 || !band_pair(s, L, blk_top(s, j, 2), &lo, &hi)) continue;
-      gm_solver* dst = ss[(k - 1) % W];
-      const u64 jd = (k - 1) / W;
-      lo &= ~63ull;
-      hi = (hi + 63) & ~63ull;
-      HIPCHK(hipMemcpyAsync(bits_at(dst, jd, B + 2, lo), bits_at(s, j, 2, lo), (hi - lo) / 8,
-                            hipMemcpyDeviceToDevice, cs));
-    }
-  }
-  return 0;
+  return exchange_ranges(ss, mode, cs, x, false, "bits halo");
 }
 
 // packed halo helpers: non-hole words of the slice pair whose first slice
@@ -816,37 +745,16 @@ static int halo_sigs_match(const std::vector<u64>& all, int world, int T) {
 }
 // gather every rank's fingerprints and compare (once per solver: the
 // geometry never changes)
-static int check_halo_plan(std::vector<gm_solver*>& ss, int mode, hipStream_t st) {
+static int check_halo_plan(std::vector<gm_solver*>& ss, Xchg mode, hipStream_t st) {
   gm_solver* s0 = ss[0];
   if (s0->halo_ok) return 0;
   const int T = s0->d.max_levels, W = s0->world;
-  std::vector<u64> all((size_t)W * T * 4);
-  if (mode == 2) {
-    for (gm_solver* s : ss)
-      for (int L = 0; L < T; L++) halo_sigs(s, (u64)L, &all[((size_t)s->rank * T + L) * 4]);
-  } else {
-    std::vector<u64> mine((size_t)T * 4);
-    for (int L = 0; L < T; L++) halo_sigs(s0, (u64)L, &mine[(size_t)L * 4]);
-    if (mode == 3) {
-      int rc = xfer_call(s0, GM_XFER_ALLGATHER, mine.data(), mine.size() * 8, -1, all.data(), all.size() * 8, -1);
-      if (rc) return rc;
-    } else {
-      void* dev = nullptr;
-      HIPCHK(hipMalloc(&dev, (all.size() + mine.size()) * 8));
-      u64* dall = (u64*)dev;
-      u64* dmine = dall + all.size();
-      hipError_t e = hipMemcpyAsync(dmine, mine.data(), mine.size() * 8, hipMemcpyHostToDevice, st);
-      ncclResult_t r = ncclSuccess;
-      if (s0->gabort && s0->gabort->load(std::memory_order_acquire)) r = ncclInvalidUsage;
-      if (e == hipSuccess && r == ncclSuccess) r = ncclAllGather(dmine, dall, mine.size(), ncclUint64, s0->comm, st);
-      if (e == hipSuccess && r == ncclSuccess) e = hipMemcpyAsync(all.data(), dall, all.size() * 8, hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipStreamSynchronize(st);
-      (void)hipFree(dev);
-      if (r != ncclSuccess) return fail(GM_EHIP, "RCCL allgather of the halo plan: %s", ncclGetErrorString(r));
-      if (e != hipSuccess) return fail(GM_EHIP, "halo plan: %s", hipGetErrorString(e));
-    }
-  }
-  int rc = halo_sigs_match(all, W, T);
+  std::vector<u64> all;
+  int rc = xchg_allgather(ss, mode, st, (size_t)T * 4, all, [&](gm_solver* s, u64* row) {
+    for (int L = 0; L < T; L++) halo_sigs(s, (u64)L, &row[(size_t)L * 4]);
+  });
+  if (rc) return rc;
+  rc = halo_sigs_match(all, W, T);
   if (rc) return rc;
   for (gm_solver* s : ss) s->halo_ok = true;
   return 0;
@@ -855,78 +763,17 @@ static int check_halo_plan(std::vector<gm_solver*>& ss, int mode, hipStream_t st
 // after resolve(L): words of every block's top two own slices go up.
 // Power-of-two tables send only the non-hole words (about a fifth of the
 // two slices, averaged over the levels).
-static int exchange_words(std::vector<gm_solver*>& ss, u64 L, int mode, hipStream_t cs) {
+static int exchange_words(std::vector<gm_solver*>& ss, u64 L, Xchg mode, hipStream_t cs) {
   bool packed = true;
   for (gm_solver* s : ss) packed = packed && s->hg.on;
   auto words_at = [&](gm_solver* s, u64 j, u64 o, u64 off) {
     return s->words + L * s->view.Wl + blk_slice(s, j, o) * s->view.Z + off;
   };
-  if (mode == 3) {  // host-staged: the RCCL form's buffers and order
-    gm_solver* s = ss[0];
-    const int down = (s->rank + s->world - 1) % s->world, up = (s->rank + 1) % s->world;
-    const u64 nb = blk_count(s), B = s->view.B;
-    std::vector<HostRange> out, in;
-    u64 nrecv = 0;
-    if (packed) {
-      const u64 wb = s->halo16 ? 2 : 4;
-      const u64 nsend = halo_move_all(s, L, 1, s->halo_send, cs);
-      HIPCHK(hipGetLastError());
-      nrecv = halo_recv_count(s, L);
-      if (nsend) out.push_back({s->halo_send, nsend * wb});
-      if (nrecv) in.push_back({s->halo_recv, nrecv * wb});
-    } else {
-      for (u64 j = 0; j < nb; j++) {
-        u64 lo, hi;
-        if (blk_global(s, j) + 1 < s->nblocks && band_pair(s, L, blk_top(s, j, B), &lo, &hi))
-          out.push_back({words_at(s, j, B, lo), (hi - lo) * 4});
-        if (blk_global(s, j) >= 1 && band_pair(s, L, blk_top(s, j, 0), &lo, &hi))
-          in.push_back({words_at(s, j, 0, lo), (hi - lo) * 4});
-      }
-    }
-    int rc = xfer_ranges(s, out, up, in, down, cs);
-    if (rc) return rc;
-    if (packed && nrecv) halo_move_all(s, L, 0, s->halo_recv, cs);
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  if (mode == 1) {
-    gm_solver* s = ss[0];
-    const int down = (s->rank + s->world - 1) % s->world, up = (s->rank + 1) % s->world;
-    const u64 nb = blk_count(s), B = s->view.B;
-    RCCL_LIVE(s);
-    if (packed) {
-      const u64 nsend = halo_move_all(s, L, 1, s->halo_send, cs);
-      const u64 nrecv = halo_recv_count(s, L);
-      ncclGroupStart();
-      const u64 wb = s->halo16 ? 2 : 4;  // bytes per packed word
-      if (nsend) ncclSend(s->halo_send, nsend * wb, ncclUint8, up, s->comm, cs);
-      if (nrecv) ncclRecv(s->halo_recv, nrecv * wb, ncclUint8, down, s->comm, cs);
-      ncclResult_t r = ncclGroupEnd();
-      if (r != ncclSuccess) return fail(GM_EHIP, "RCCL words halo: %s", ncclGetErrorString(r));
-      if (nrecv) halo_move_all(s, L, 0, s->halo_recv, cs);
-      HIPCHK(hipGetLastError());
-      return 0;
-    }
-    ncclGroupStart();
-    for (u64 j = 0; j < nb; j++) {
-      u64 lo, hi;
-      if (blk_global(s, j) + 1 < s->nblocks && band_pair(s, L, blk_top(s, j, B), &lo, &hi))
-        ncclSend(words_at(s, j, B, lo), (hi - lo) * 4, ncclUint8, up, s->comm, cs);
-    }
-    for (u64 j = 0; j < nb; j++) {
-      u64 lo, hi;
-      if (blk_global(s, j) >= 1 && band_pair(s, L, blk_top(s, j, 0), &lo, &hi))
-        ncclRecv(words_at(s, j, 0, lo), (hi - lo) * 4, ncclUint8, down, s->comm, cs);
-    }
-    ncclResult_t r = ncclGroupEnd();
-    if (r != ncclSuccess) return fail(GM_EHIP, "RCCL words halo: %s", ncclGetErrorString(r));
-    return 0;
-  }
-  const int W = (int)ss.size();
-  if (packed) {
+  if (packed && xchg_group(mode)) {
     // every block of shard g sends to shard g + 1 (mod W): pack straight
     // into the receiver's buffer, then unpack there -- the RCCL path's
     // kernels and order, with the transfer left out
+    const int W = (int)ss.size();
     for (int g = 0; g < W; g++) {
       gm_solver* dst = ss[(g + 1) % W];
       const u64 n = halo_move_all(ss[g], L, 1, dst->halo_recv, cs);
@@ -941,20 +788,35 @@ static int exchange_words(std::vector<gm_solver*>& ss, u64 L, int mode, hipStrea
     HIPCHK(hipGetLastError());
     return 0;
   }
-  for (gm_solver* s : ss) {
+  std::vector<XLists> x(ss.size());
+  if (packed) {  // one shard: its packed send buffer up, the packed receive buffer from below
+    gm_solver* s = ss[0];
+    if (mode == XCHG_RCCL) RCCL_LIVE(s);
+    const u64 wb = s->halo16 ? 2 : 4;  // bytes per packed word
+    const u64 nsend = halo_move_all(s, L, 1, s->halo_send, cs);
+    HIPCHK(hipGetLastError());
+    const u64 nrecv = halo_recv_count(s, L);
+    x[0].out.push_back({ring_up(s), s->halo_send, nsend * wb});
+    x[0].in.push_back({ring_down(s), s->halo_recv, nrecv * wb});
+    int rc = exchange_ranges(ss, mode, cs, x, true, "words halo");
+    if (rc) return rc;
+    if (nrecv) halo_move_all(s, L, 0, s->halo_recv, cs);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  for (size_t g = 0; g < ss.size(); g++) {
+    gm_solver* s = ss[g];
     const u64 nb = blk_count(s), B = s->view.B;
     for (u64 j = 0; j < nb; j++) {
-      const u64 k = blk_global(s, j);
-      if (k + 1 >= s->nblocks) continue;
-      gm_solver* dst = ss[(k + 1) % W];
-      const u64 jd = (k + 1) / W;
-      const int64_t t0 = blk_top(s, j, B);
       u64 lo, hi;
-      if (!band_pair(s, L, t0, &lo, &hi)) continue;
-      HIPCHK(hipMemcpyAsync(words_at(dst, jd, 0, lo), words_at(s, j, B, lo), (hi - lo) * 4,
-                            hipMemcpyDeviceToDevice, cs));
+      if (blk_global(s, j) + 1 < s->nblocks && band_pair(s, L, blk_top(s, j, B), &lo, &hi))
+        x[g].out.push_back({ring_up(s), words_at(s, j, B, lo), (hi - lo) * 4});
+      if (blk_global(s, j) >= 1 && band_pair(s, L, blk_top(s, j, 0), &lo, &hi))
+        x[g].in.push_back({ring_down(s), words_at(s, j, 0, lo), (hi - lo) * 4});
     }
   }
+  int rc = exchange_ranges(ss, mode, cs, x, true, "words halo");
+  if (rc) return rc;
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -967,9 +829,7 @@ static int exchange_words(std::vector<gm_solver*>& ss, u64 L, int mode, hipStrea
 struct DenseSolve {
   std::vector<gm_solver*>& ss;
   gm_solver* s0;
-  // 0: one table; 1: one shard per process over RCCL; 2: in-process group;
-  // 3: one shard per process over a host-staged transport
-  int mode = 0;
+  Xchg mode = XCHG_TABLE;          // (never XCHG_STREAMS: a dense group runs on one stream)
   int T = 0, first = 0, stop = 0;  // levels; the steps [first, stop) of 2T (gm_solver_set_steps, world 1 only)
   bool timing = false;             // GM_F_KERNEL_TIMING (whole solves): ev.kx / ev.kr around shard 0's launches
   bool pipe = false;               // the halo exchanges overlap compute on the stream cs
@@ -993,17 +853,13 @@ static int dense_solve_begin(DenseSolve& c) {
   gm_solver* s0 = c.s0;
   const Desc& d = s0->d;
   const int T = c.T = d.max_levels;
-  const int mode = c.mode = s0->world <= 1 ? 0 : ss.size() != 1 ? 2 : s0->xfer ? 3 : 1;
-  if (mode == 1 && !s0->comm) return fail(GM_EINVAL, "shard %d/%d has no communicator (gm_solver_comm_init)", s0->rank, s0->world);
-  if (mode == 2) {
-    if ((int)ss.size() != s0->world) return fail(GM_EINVAL, "group solve needs all %d shards", s0->world);
-    for (size_t g = 0; g < ss.size(); g++)
-      if (ss[g]->rank != (int)g || ss[g]->stream != s0->stream || ss[g]->mode != GM_MODE_DENSE)
-        return fail(GM_EINVAL, "group shards must be ranks 0..n-1 on one stream");
-  }
+  int rc = xchg_mode(ss, GM_MODE_DENSE, &c.mode);
+  if (rc) return rc;
+  const Xchg mode = c.mode;
+  if (mode == XCHG_STREAMS) return fail(GM_EINVAL, "dense group shards run on one stream");
   // forward level L is step L, backward level L is step 2T-1-L
-  c.first = mode == 0 ? (int)s0->step_first : 0;
-  c.stop = mode == 0 && s0->step_stop ? (int)s0->step_stop : 2 * T;
+  c.first = mode == XCHG_TABLE ? (int)s0->step_first : 0;
+  c.stop = mode == XCHG_TABLE && s0->step_stop ? (int)s0->step_stop : 2 * T;
   s0->step_first = s0->step_stop = 0;
   c.timing = (s0->flags & GM_F_KERNEL_TIMING) && c.whole();
   c.st = s0->stream;
@@ -1029,7 +885,7 @@ static int dense_solve_begin(DenseSolve& c) {
   // halo.  Per level: own part -> event -> exchange on the comm stream ->
   // event; the boundary part of the NEXT level waits for that exchange.  A
   // block narrower than 4 top values has no such split: exchange in order.
-  c.pipe = mode == 1 || mode == 2;  // the host-staged transport runs in order
+  c.pipe = mode == XCHG_RCCL || mode == XCHG_GROUP;  // the host-staged transport runs in order
   for (gm_solver* s : ss)
     if (s->view.B < 4) c.pipe = false;
   if (s0->flags & GM_F_SHARD_INORDER) c.pipe = false;  // A/B: exchange in order
@@ -1045,17 +901,14 @@ static int dense_solve_begin(DenseSolve& c) {
     c.E = s0->pev.data();
   }
   for (int i = 1; i + 1 < d.nheaps; i++) c.slow += (int)d.heap[i];
-  if (mode != 0) {
-    int rc = check_halo_plan(ss, mode, c.st);
-    if (rc) return rc;
-  }
+  if (mode != XCHG_TABLE && (rc = check_halo_plan(ss, mode, c.st))) return rc;
   // Tail runs (one table, whole solves, live-group lists, 8-bit words): the
   // levels at both ends whose live groups fit a workgroup in a pass or two
   // run as one single-workgroup launch each (k_dense_pull_tail,
   // k_dense_resolve16_tail).  A kernel-timing solve keeps one launch per
   // level, so per-launch figures (bench roofline, PMC passes of a timed solve)
   // describe the per-level kernels alone.
-  const bool tails = mode == 0 && !c.timing && c.whole() && s0->glist && !s0->view.blk && s0->pk == PK_WORDS &&
+  const bool tails = mode == XCHG_TABLE && !c.timing && c.whole() && s0->glist && !s0->view.blk && s0->pk == PK_WORDS &&
                      s0->w8 && d.pow2;
   c.pb = c.ra = T;
   if (tails) {
@@ -1126,7 +979,8 @@ static DenseView dense_level_view(const DenseSolve& c, const gm_solver* s, int L
 // slices [b-2, b), whose parents sit in the halo [b, b+2) sent down by the
 // rank above.
 static int dense_forward(DenseSolve& c) {
-  const int T = c.T, mode = c.mode;
+  const int T = c.T;
+  const Xchg mode = c.mode;
   const bool pipe = c.pipe, timing = c.timing;
   hipStream_t st = c.st, cs = c.cs;
   hipEvent_t* E = c.E;
@@ -1146,7 +1000,7 @@ static int dense_forward(DenseSolve& c) {
       const DenseView own = dense_level_view(c, s, L, 2, pipe ? B : B + 2);
       if (own.p_hi > own.p_lo) dense_launch_pull(s, own, dense_grid_of(s, own), (u64)L, c.root_p);
     }
-    if (mode) {
+    if (mode != XCHG_TABLE) {
       if (pipe) {
         HIPCHK(hipEventRecord(E[L], st));
         HIPCHK(hipStreamWaitEvent(cs, E[L], 0));
@@ -1173,7 +1027,8 @@ static int dense_forward(DenseSolve& c) {
 // boundary is the bottom two slices [a, a+2), whose children sit in the
 // halo [a-2, a) sent up by the rank below.
 static int dense_backward(DenseSolve& c) {
-  const int T = c.T, mode = c.mode;
+  const int T = c.T;
+  const Xchg mode = c.mode;
   const bool pipe = c.pipe, timing = c.timing;
   hipStream_t st = c.st, cs = c.cs;
   hipEvent_t* E = c.E;
@@ -1188,7 +1043,7 @@ static int dense_backward(DenseSolve& c) {
       const DenseView own = dense_level_view(c, s, L, pipe ? 4 : 2, B + 2);
       if (own.p_hi > own.p_lo) dense_launch_resolve(s, own, dense_grid_of(s, own), (u64)L);
     }
-    if (mode) {
+    if (mode != XCHG_TABLE) {
       if (pipe) {
         HIPCHK(hipEventRecord(E[L], st));
         HIPCHK(hipStreamWaitEvent(cs, E[L], 0));
@@ -1255,7 +1110,8 @@ static int dense_graphs(DenseSolve& c) {
 static int dense_finish(DenseSolve& c, gm_result* out) {
   std::vector<gm_solver*>& ss = c.ss;
   gm_solver* s0 = c.s0;
-  const int T = c.T, mode = c.mode;
+  const int T = c.T;
+  const Xchg mode = c.mode;
   hipStream_t st = c.st;
   for (gm_solver* s : ss) {
     uint64_t root_q = ~0ull;
@@ -1263,37 +1119,14 @@ static int dense_finish(DenseSolve& c, gm_result* out) {
     hipLaunchKernelGGL(k_dense_root, dim3(1), dim3(64), 0, st, s->view, s->words, s->bits, root_q, s->st, s->wbits());
     hipLaunchKernelGGL(k_fill_red, dim3(1), dim3(1024), 0, st, s->st, s->bcount);
   }
-  if (mode == 1) {  // counts and root word summed; every rank's error mask gathered, OR-ed on the host
-    RCCL_LIVE(s0);
-    ncclGroupStart();
-    ncclResult_t r = ncclAllReduce(s0->st->red, s0->st->red, 4, ncclUint64, ncclSum, s0->comm, st);
-    ncclResult_t r2 = ncclAllGather(s0->st->red + 4, s0->errg, 1, ncclUint64, s0->comm, st);
-    ncclResult_t r3 = ncclGroupEnd();
-    if (r != ncclSuccess || r2 != ncclSuccess || r3 != ncclSuccess)
-      return fail(GM_EHIP, "RCCL allreduce: %s", ncclGetErrorString(r != ncclSuccess ? r : r2 != ncclSuccess ? r2 : r3));
-  }
-  // totals (host): RCCL has already reduced red[] across ranks; a group and
-  // the host-staged transport reduce here (counts summed, error masks OR-ed)
-  u64 red[5] = {0, 0, 0, 0, 0};
+  int rc = mode == XCHG_RCCL ? xchg_reduce_rccl(s0, st) : 0;
+  if (rc) return rc;
+  u64 red[5] = {0, 0, 0, 0, 0};  // the job's totals
   for (gm_solver* s : ss) {
     u64 r[5];
     HIPCHK(hipMemcpyAsync(r, s->st->red, sizeof r, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (mode == 3) {
-      std::vector<u64> all((size_t)5 * s->world);
-      int rc = xfer_call(s, GM_XFER_ALLGATHER, r, sizeof r, -1, all.data(), all.size() * 8, -1);
-      if (rc) return rc;
-      for (int g = 0; g < s->world; g++)
-        for (int i = 0; i < 5; i++) red[i] = (i == 4) ? (red[i] | all[(size_t)g * 5 + i]) : red[i] + all[(size_t)g * 5 + i];
-      continue;
-    }
-    if (mode == 1) {
-      std::vector<u64> e((size_t)s->world);
-      HIPCHK(hipMemcpy(e.data(), s->errg, e.size() * sizeof(u64), hipMemcpyDeviceToHost));
-      r[4] = 0;
-      for (u64 x : e) r[4] |= x;
-    }
-    for (int i = 0; i < 5; i++) red[i] = (i == 4) ? (red[i] | r[i]) : red[i] + r[i];
+    if ((rc = xchg_reduce_fold(s, mode, r, red))) return rc;
   }
   auto t1 = std::chrono::steady_clock::now();
   float f = 0, b = 0;
@@ -1331,7 +1164,7 @@ static int run_dense(std::vector<gm_solver*> ss, gm_result* out) {
   gm_solver* s0 = c.s0;
   int rc = dense_solve_begin(c);
   if (rc) return rc;
-  const bool graphed = (s0->flags & GM_F_GRAPH) && c.mode == 0 && !c.timing && c.whole();
+  const bool graphed = (s0->flags & GM_F_GRAPH) && c.mode == XCHG_TABLE && !c.timing && c.whole();
   if (graphed && !s0->gfwd && (rc = dense_graphs(c))) return rc;
   const bool replay = graphed && s0->gfwd && s0->gbwd;
   hipStream_t st = c.st, cs = c.cs;

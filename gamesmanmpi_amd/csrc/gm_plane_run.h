@@ -1029,85 +1029,33 @@ static void plane_sigs(const gm_solver* s, u64* out) {
 
 // exchange the boundary planes of level l: every shard sends its (l, p)
 // send segment to each peer p and receives each peer q's into its (l, q)
-// receive segment (mode 1 RCCL, one grouped send/recv set; 2 in-process
-// copies; 3 host-staged, world - 1 shifted pairwise rounds)
-static int plane_exchange(std::vector<gm_solver*>& ss, uint32_t l, int mode, hipStream_t cs) {
+// receive segment (RCCL: one grouped send / receive set; a group: device
+// copies; the host transport: world - 1 shifted pairwise rounds)
+static int plane_exchange(std::vector<gm_solver*>& ss, uint32_t l, Xchg mode, hipStream_t cs) {
   const u64 pb = 1024ull * ss[0]->pwb;
   const int W = ss[0]->world;
-  if (mode == 2) {
-    for (int r = 0; r < W; r++)
-      for (int p = 0; p < W; p++) {
-        gm_solver* a = ss[(size_t)r];
-        gm_solver* b = ss[(size_t)p];
-        u64 ns, nr;
-        const u64 so = plane_seg(a->psnd_off, l, W, p, &ns), ro = plane_seg(b->prcv_off, l, W, r, &nr);
-        if (ns != nr) return fail(GM_ECORRUPT, "level %u: shard %d sends %llu planes, shard %d expects %llu", l, r,
-                                  (unsigned long long)ns, p, (unsigned long long)nr);
-        if (ns)
-          HIPCHK(hipMemcpyAsync((char*)b->precv + ro * pb, (const char*)a->psend + so * pb, ns * pb,
-                                hipMemcpyDeviceToDevice, cs));
-      }
-    return 0;
-  }
-  gm_solver* s = ss[0];
-  auto sbuf = [&](int p, u64* n) { return (void*)((char*)s->psend + plane_seg(s->psnd_off, l, W, p, n) * pb); };
-  auto rbuf = [&](int p, u64* n) { return (void*)((char*)s->precv + plane_seg(s->prcv_off, l, W, p, n) * pb); };
-  if (mode == 1) {
-    RCCL_LIVE(s);
-    ncclResult_t r = ncclGroupStart();
-    for (int p = 0; p < W && r == ncclSuccess; p++) {
+  std::vector<XLists> x(ss.size());
+  for (size_t g = 0; g < ss.size(); g++) {
+    gm_solver* s = ss[g];
+    for (int p = 0; p < W; p++) {
       u64 ns, nr;
-      void* sb = sbuf(p, &ns);
-      void* rb = rbuf(p, &nr);
-      if (ns) r = ncclSend(sb, ns * pb, ncclUint8, p, s->comm, cs);
-      if (nr && r == ncclSuccess) r = ncclRecv(rb, nr * pb, ncclUint8, p, s->comm, cs);
+      const u64 so = plane_seg(s->psnd_off, l, W, p, &ns), ro = plane_seg(s->prcv_off, l, W, p, &nr);
+      x[g].out.push_back({p, (char*)s->psend + so * pb, ns * pb});
+      x[g].in.push_back({p, (char*)s->precv + ro * pb, nr * pb});
     }
-    const ncclResult_t r2 = ncclGroupEnd();
-    if (r != ncclSuccess || r2 != ncclSuccess)
-      return fail(GM_EHIP, "RCCL halo exchange: %s", ncclGetErrorString(r != ncclSuccess ? r : r2));
-    return 0;
   }
-  for (int k = 1; k < W; k++) {
-    const int to = (s->rank + k) % W, from = (s->rank + W - k) % W;
-    u64 ns, nr;
-    void* sb = sbuf(to, &ns);
-    void* rb = rbuf(from, &nr);
-    std::vector<HostRange> out, in;
-    if (ns) out.push_back({sb, ns * pb});
-    if (nr) in.push_back({rb, nr * pb});
-    int rc = xfer_ranges(s, out, to, in, from, cs);
-    if (rc) return rc;
-  }
-  return 0;
+  if (xchg_group(mode)) return xchg_copies(ss, mode, cs, x);
+  return xchg_ranges(ss[0], mode, cs, x[0], xchg_rounds(ss[0]->rank, W), "halo exchange");
 }
 
 // before the first sharded solve: every shard's sends to each peer must
 // match that peer's receives from it (fingerprints all-gathered)
-static int plane_check_plan(std::vector<gm_solver*>& ss, int mode, hipStream_t st) {
+static int plane_check_plan(std::vector<gm_solver*>& ss, Xchg mode, hipStream_t st) {
   const int W = ss[0]->world;
   const size_t m = (size_t)2 * W;  // fingerprints per shard
-  std::vector<u64> all(m * W);
-  if (mode == 2) {
-    for (gm_solver* s : ss) plane_sigs(s, &all[m * s->rank]);
-  } else {
-    std::vector<u64> mine(m);
-    plane_sigs(ss[0], mine.data());
-    if (mode == 3) {
-      int rc = xfer_call(ss[0], GM_XFER_ALLGATHER, mine.data(), m * 8, -1, all.data(), all.size() * 8, -1);
-      if (rc) return rc;
-    } else {
-      RCCL_LIVE(ss[0]);
-      u64* dev = nullptr;
-      HIPCHK(hipMalloc((void**)&dev, (m + all.size()) * 8));
-      HIPCHK(hipMemcpyAsync(dev, mine.data(), m * 8, hipMemcpyHostToDevice, st));
-      ncclResult_t r = ncclAllGather(dev, dev + m, m, ncclUint64, ss[0]->comm, st);
-      hipError_t e = hipMemcpyAsync(all.data(), dev + m, all.size() * 8, hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipStreamSynchronize(st);
-      (void)hipFree(dev);
-      if (r != ncclSuccess) return fail(GM_EHIP, "RCCL plan check: %s", ncclGetErrorString(r));
-      if (e != hipSuccess) return fail(GM_EHIP, "plan check: %s", hipGetErrorString(e));
-    }
-  }
+  std::vector<u64> all;
+  int rc = xchg_allgather(ss, mode, st, m, all, [](gm_solver* s, u64* row) { plane_sigs(s, row); });
+  if (rc) return rc;
   for (int r = 0; r < W; r++)
     for (int p = 0; p < W; p++)
       if (all[m * r + 2 * p] != all[m * p + 2 * r + 1])
@@ -1133,29 +1081,11 @@ static u64 plane_stage_sig(const gm_solver* s) {
   for (u64 v : rows) mix(v);
   return h;
 }
-static int plane_check_stage(std::vector<gm_solver*>& ss, int mode, hipStream_t st) {
+static int plane_check_stage(std::vector<gm_solver*>& ss, Xchg mode, hipStream_t st) {
   const int W = ss[0]->world;
-  std::vector<u64> all((size_t)W);
-  if (mode == 2 || mode == 4) {
-    for (gm_solver* s : ss) all[(size_t)s->rank] = plane_stage_sig(s);
-  } else {
-    u64 mine = plane_stage_sig(ss[0]);
-    if (mode == 3) {
-      int rc = xfer_call(ss[0], GM_XFER_ALLGATHER, &mine, 8, -1, all.data(), all.size() * 8, -1);
-      if (rc) return rc;
-    } else {
-      RCCL_LIVE(ss[0]);
-      u64* dev = nullptr;
-      HIPCHK(hipMalloc((void**)&dev, (size_t)(1 + W) * 8));
-      HIPCHK(hipMemcpyAsync(dev, &mine, 8, hipMemcpyHostToDevice, st));
-      ncclResult_t r = ncclAllGather(dev, dev + 1, 1, ncclUint64, ss[0]->comm, st);
-      hipError_t e = hipMemcpyAsync(all.data(), dev + 1, all.size() * 8, hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipStreamSynchronize(st);
-      (void)hipFree(dev);
-      if (r != ncclSuccess) return fail(GM_EHIP, "RCCL plan check: %s", ncclGetErrorString(r));
-      if (e != hipSuccess) return fail(GM_EHIP, "plan check: %s", hipGetErrorString(e));
-    }
-  }
+  std::vector<u64> all;
+  int rc = xchg_allgather(ss, mode, st, 1, all, [](gm_solver* s, u64* row) { *row = plane_stage_sig(s); });
+  if (rc) return rc;
   for (int r = 1; r < W; r++)
     if (all[(size_t)r] != all[0])
       return fail(GM_ECORRUPT, "staged plan mismatch: shard %d's geometry differs from shard 0's", r);
@@ -1224,7 +1154,7 @@ static int staged_defer(gm_solver* s, int herr, hipStream_t st) {
 // error word, which the end-of-solve reduction hands to every rank, and
 // reports its own error there (s->defer_rc).  Only a failed transfer call
 // returns at once: the exchange itself is then broken.
-static int plane_backward_staged(std::vector<gm_solver*>& ss, int mode, hipStream_t st, u64* nlaunch) {
+static int plane_backward_staged(std::vector<gm_solver*>& ss, Xchg mode, hipStream_t st, u64* nlaunch) {
   gm_solver* s0 = ss[0];
   // (the row deal: key = row = plane level, each final after its own key --
   // a lag of B - 1 = 0 -- and two rows per plane in the halo)
@@ -1253,7 +1183,7 @@ static int plane_backward_staged(std::vector<gm_solver*>& ss, int mode, hipStrea
     const uint32_t rs = rowdeal ? key & 3u : kPlaneRsVisit;
     pb_.add(o[key], o[(size_t)key + 1], rs, key + 1 < K ? o[(size_t)key + 2] - o[(size_t)key + 1] : 0);
   };
-  if (mode == 2) {
+  if (mode == XCHG_GROUP) {
     for (int c = 0; c < W; c++) {
       gm_solver* s = ss[(size_t)c];
       PlaneBatcher bat(s);
@@ -1277,7 +1207,7 @@ static int plane_backward_staged(std::vector<gm_solver*>& ss, int mode, hipStrea
     }
     return 0;
   }
-  if (mode == 3) {
+  if (mode == XCHG_HOST) {
     gm_solver* s = s0;
     PlaneBatcher bat(s);
     const int rank = s->rank;
@@ -1385,7 +1315,7 @@ static int plane_backward_staged(std::vector<gm_solver*>& ss, int mode, hipStrea
       }
     }
     bat.flush();
-    if (rank == 0 || mode == 1) *nlaunch = bat.launches;
+    if (rank == 0 || mode == XCHG_RCCL) *nlaunch = bat.launches;
     int rc = post_to(R);
     if (rc) return rc;
     dchk(hipEventRecord(XE[1], ts), "hipEventRecord");
@@ -1394,7 +1324,7 @@ static int plane_backward_staged(std::vector<gm_solver*>& ss, int mode, hipStrea
     dchk(hipStreamWaitEvent(cst, XE[2], 0), "hipStreamWaitEvent");
     return staged_defer(s, herr, cst);
   };
-  if (mode == 4) {
+  if (mode == XCHG_STREAMS) {
     // the ranks' host loops in pipeline order (a row's XS event exists before
     // the next rank's receive waits on it); every rank on its own streams of
     // the one GPU, so its keys overlap the ranks before it as on separate
@@ -1516,10 +1446,7 @@ struct PlaneSolve {
   std::vector<gm_solver*>& ss;
   gm_solver* s0;
   bool async;  // queued (gm_solver_solve_async)
-  // 0: one table; 1: one shard per process, RCCL; 2: a group on ONE stream;
-  // 3: one shard per process, host-staged transport; 4: a group whose shards
-  // have their own streams -- the rehearsal of mode 1's staged schedule
-  int mode = 0;
+  Xchg mode = XCHG_TABLE;  // (XCHG_STREAMS: the rehearsal of the RCCL staged schedule)
   int T = 0, first = 0, stop = 0;  // levels; the steps [first, stop) of 2T (gm_solver_set_steps, one table only)
   uint32_t S = 0;                  // largest plane level
   bool timing = false;             // GM_F_KERNEL_TIMING (whole blocking solves)
@@ -1538,21 +1465,21 @@ struct PlaneSolve {
   // level's launches (exchanges sit between them); else one pair around the
   // whole backward (no events between launches: they would add their own
   // gaps to what they time)
-  bool per_level() const { return timing && mode != 0 && !staged; }
+  bool per_level() const { return timing && mode != XCHG_TABLE && !staged; }
 };
 
 // mode 4: the shards' own streams fork from st after e0 and join it before
 // e1, fork again for the backward and join before e2 (other modes: every
 // shard runs on st)
 static int plane_fork(PlaneSolve& c) {
-  if (c.mode != 4) return 0;
+  if (c.mode != XCHG_STREAMS) return 0;
   HIPCHK(hipEventRecord(c.ev.ef, c.st));
   for (gm_solver* s : c.ss)
     if (s->stream != c.st) HIPCHK(hipStreamWaitEvent(s->stream, c.ev.ef, 0));
   return 0;
 }
 static int plane_join(PlaneSolve& c) {
-  if (c.mode != 4) return 0;
+  if (c.mode != XCHG_STREAMS) return 0;
   for (size_t g = 0; g < c.ss.size(); g++)
     if (c.ss[g]->stream != c.st) {
       HIPCHK(hipEventRecord(c.ev.ej[g], c.ss[g]->stream));
@@ -1568,26 +1495,16 @@ static int plane_solve_begin(PlaneSolve& c) {
   gm_solver* s0 = c.s0;
   c.T = s0->d.max_levels;
   c.S = s0->pS;
-  const bool own_streams = ss.size() > 1 && ss[1]->stream != s0->stream;
-  const int mode = c.mode = s0->world <= 1 ? 0 : ss.size() != 1 ? (own_streams ? 4 : 2) : s0->xfer ? 3 : 1;
-  if (mode == 1 && !s0->comm) return fail(GM_EINVAL, "shard %d/%d has no communicator (gm_solver_comm_init)", s0->rank, s0->world);
-  if (mode == 2 || mode == 4) {
-    if ((int)ss.size() != s0->world) return fail(GM_EINVAL, "group solve needs all %d shards", s0->world);
-    for (size_t g = 0; g < ss.size(); g++) {
-      if (ss[g]->rank != (int)g || ss[g]->mode != GM_MODE_PLANES)
-        return fail(GM_EINVAL, "group shards must be ranks 0..n-1");
-      for (size_t h = 0; h < g; h++)
-        if ((mode == 2) != (ss[g]->stream == ss[h]->stream))
-          return fail(GM_EINVAL, "group shards share one stream, or (the staged rehearsal) each has its own");
-    }
-    if (mode == 4 && !s0->pstage_k)
-      return fail(GM_EINVAL, "shards on their own streams rehearse the staged deal only (this shape is level-synchronous)");
-  }
-  c.first = mode == 0 ? (int)s0->step_first : 0;
-  c.stop = mode == 0 && s0->step_stop ? (int)s0->step_stop : 2 * c.T;
+  int rc = xchg_mode(ss, GM_MODE_PLANES, &c.mode);
+  if (rc) return rc;
+  const Xchg mode = c.mode;
+  if (mode == XCHG_STREAMS && !s0->pstage_k)
+    return fail(GM_EINVAL, "shards on their own streams rehearse the staged deal only (this shape is level-synchronous)");
+  c.first = mode == XCHG_TABLE ? (int)s0->step_first : 0;
+  c.stop = mode == XCHG_TABLE && s0->step_stop ? (int)s0->step_stop : 2 * c.T;
   s0->step_first = s0->step_stop = 0;
   c.timing = (s0->flags & GM_F_KERNEL_TIMING) && c.whole();
-  if (c.async && (mode != 0 || !c.whole() || c.timing))
+  if (c.async && (mode != XCHG_TABLE || !c.whole() || c.timing))
     return fail(GM_EINVAL, "queued solves: one-table PLANES full solves without kernel timing only");
   c.st = s0->stream;
   if (c.first > 0) {
@@ -1597,15 +1514,14 @@ static int plane_solve_begin(PlaneSolve& c) {
       return fail(GM_EINVAL, "resume: the scratch holds no %u-bit%s planes solve", 8 * s0->pwb,
                   s0->pform == 3 ? " relative" : "");
   }
-  c.staged = mode != 0 && s0->pstage_k;
+  c.staged = mode != XCHG_TABLE && s0->pstage_k;
   for (gm_solver* s : ss) {
     s->defer_rc = 0;
     s->defer_msg.clear();
   }
-  if (mode != 0 && !s0->halo_ok) {
-    int rc = c.staged ? plane_check_stage(ss, mode, c.st) : plane_check_plan(ss, mode, c.st);
-    if (rc) return rc;
-  }
+  if (mode != XCHG_TABLE && !s0->halo_ok &&
+      (rc = c.staged ? plane_check_stage(ss, mode, c.st) : plane_check_plan(ss, mode, c.st)))
+    return rc;
   // the solve's timing events live with the solver (created once: a create +
   // destroy per event per solve was host time between solves); a queued
   // solve uses its ring slot's own
@@ -1622,7 +1538,7 @@ static int plane_solve_begin(PlaneSolve& c) {
     HIPCHK(hipEventCreate(&c.ev.kx[0]));
     HIPCHK(hipEventCreate(&c.ev.kx[1]));
   }
-  if (mode == 4) {
+  if (mode == XCHG_STREAMS) {
     HIPCHK(hipEventCreate(&c.ev.ef));
     c.ev.ej.assign(ss.size(), nullptr);
     for (hipEvent_t& e : c.ev.ej) HIPCHK(hipEventCreate(&e));
@@ -1630,7 +1546,7 @@ static int plane_solve_begin(PlaneSolve& c) {
   // one table, whole solve: the backward as ONE launch (k_plane_flow,
   // gm_plane.h) -- GM_F_PLANE_LEVELS keeps the per-level launches (A/B), and
   // partial / resumed solves take them
-  c.flow = mode == 0 && s0->pflow_ok && c.whole() && !(s0->flags & (GM_F_PLANE_LEVELS | GM_F_PLANE_X1));
+  c.flow = mode == XCHG_TABLE && s0->pflow_ok && c.whole() && !(s0->flags & (GM_F_PLANE_LEVELS | GM_F_PLANE_X1));
   // One table, whole solve, per-level backward: the forward -- state and
   // count-slot resets, reach map + counts -- runs on a side stream BESIDE the
   // backward, which never reads any of it (a plane's words follow from its
@@ -1643,7 +1559,7 @@ static int plane_solve_begin(PlaneSolve& c) {
   // per 2^30 solve) or at its narrow tail (1.40 ms);
   // profiles/r06/forward_placement_probe.txt.  So does the one-launch
   // backward: the forward's state reset must not race its error bit.
-  c.overlap = mode == 0 && c.whole() && !c.timing && !c.async && !c.flow;
+  c.overlap = mode == XCHG_TABLE && c.whole() && !c.timing && !c.async && !c.flow;
   c.fs = c.st;
   if (c.overlap) {
     if (!s0->cstream) HIPCHK(hipStreamCreateWithFlags(&s0->cstream, hipStreamNonBlocking));
@@ -1803,7 +1719,7 @@ static int plane_levels_inorder(PlaneSolve& c) {
 }
 
 static bool plane_pipelined(const PlaneSolve& c) {
-  return (c.mode == 1 || c.mode == 2) && !c.staged && c.s0->pg.B >= 4 && !(c.s0->flags & GM_F_SHARD_INORDER);
+  return (c.mode == XCHG_RCCL || c.mode == XCHG_GROUP) && !c.staged && c.s0->pg.B >= 4 && !(c.s0->flags & GM_F_SHARD_INORDER);
 }
 // Level-synchronous shards (RCCL or in-process copies), pipelined: each
 // level's launch is split into the planes that read no halo plane -- the
@@ -1851,7 +1767,7 @@ static int plane_solve_finish(PlaneSolve& c, gm_result* out) {
   {
     const hipError_t e = hipGetLastError();  // (a failed launch of the backward)
     if (e != hipSuccess) {
-      if (!c.staged || c.mode == 2) return fail(GM_EHIP, "plane backward: %s", hipGetErrorString(e));
+      if (!c.staged || c.mode == XCHG_GROUP) return fail(GM_EHIP, "plane backward: %s", hipGetErrorString(e));
       // staged shards: deferred, so the end-of-solve reduction is still entered
       if (!s0->defer_rc) staged_defer(s0, fail(GM_EHIP, "plane backward: %s", hipGetErrorString(e)), st);
     }
@@ -1893,16 +1809,9 @@ static int plane_solve_finish(PlaneSolve& c, gm_result* out) {
 static int plane_solve_reduce(PlaneSolve& c, gm_result* out) {
   gm_solver* s0 = c.s0;
   hipStream_t st = c.st;
-  const int mode = c.mode;
-  if (mode == 1) {
-    RCCL_LIVE(s0);
-    ncclGroupStart();
-    ncclResult_t r = ncclAllReduce(s0->st->red, s0->st->red, 4, ncclUint64, ncclSum, s0->comm, st);
-    ncclResult_t r2 = ncclAllGather(s0->st->red + 4, s0->errg, 1, ncclUint64, s0->comm, st);
-    ncclResult_t r3 = ncclGroupEnd();
-    if (r != ncclSuccess || r2 != ncclSuccess || r3 != ncclSuccess)
-      return fail(GM_EHIP, "RCCL allreduce: %s", ncclGetErrorString(r != ncclSuccess ? r : r2 != ncclSuccess ? r2 : r3));
-  }
+  const Xchg mode = c.mode;
+  int rc = mode == XCHG_RCCL ? xchg_reduce_rccl(s0, st) : 0;
+  if (rc) return rc;
   u64 red[5] = {0, 0, 0, 0, 0};
   for (gm_solver* s : c.ss) {
     u64 r[5];
@@ -1910,23 +1819,9 @@ static int plane_solve_reduce(PlaneSolve& c, gm_result* out) {
     // for inside the copy call)
     if (!s->phost) HIPCHK(hipHostMalloc((void**)&s->phost, 8 * sizeof(u64), hipHostMallocDefault));
     if (!c.flow) HIPCHK(hipMemcpyAsync(s->phost, s->st->red, sizeof r, hipMemcpyDeviceToHost, st));
-    HIPCHK(mode == 0 ? plane_wait(st) : hipStreamSynchronize(st));
+    HIPCHK(mode == XCHG_TABLE ? plane_wait(st) : hipStreamSynchronize(st));
     memcpy(r, s->phost, sizeof r);
-    if (mode == 3) {
-      std::vector<u64> all((size_t)5 * s->world);
-      int rc = xfer_call(s, GM_XFER_ALLGATHER, r, sizeof r, -1, all.data(), all.size() * 8, -1);
-      if (rc) return rc;
-      for (int g = 0; g < s->world; g++)
-        for (int i = 0; i < 5; i++) red[i] = (i == 4) ? (red[i] | all[(size_t)g * 5 + i]) : red[i] + all[(size_t)g * 5 + i];
-      continue;
-    }
-    if (mode == 1) {
-      std::vector<u64> e((size_t)s->world);
-      HIPCHK(hipMemcpy(e.data(), s->errg, e.size() * sizeof(u64), hipMemcpyDeviceToHost));
-      r[4] = 0;
-      for (u64 x : e) r[4] |= x;
-    }
-    for (int i = 0; i < 5; i++) red[i] = (i == 4) ? (red[i] | r[i]) : red[i] + r[i];
+    if ((rc = xchg_reduce_fold(s, mode, r, red))) return rc;
   }
   auto t1 = std::chrono::steady_clock::now();
   float f = 0, b = 0;
@@ -1971,7 +1866,7 @@ static int run_planes(std::vector<gm_solver*> ss, gm_result* out, bool async = f
   c.s0->pflow_last = c.flow;
   if (c.flow) rc = plane_backward_flow(c);
   else if (c.staged) rc = plane_backward_staged_solve(c);
-  else if (c.mode == 0) rc = plane_levels_table(c);
+  else if (c.mode == XCHG_TABLE) rc = plane_levels_table(c);
   else if (plane_pipelined(c)) rc = plane_levels_piped(c);
   else rc = plane_levels_inorder(c);
   if (rc) return rc;

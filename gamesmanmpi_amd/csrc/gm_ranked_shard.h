@@ -281,15 +281,14 @@ static int run_ranked_shards(std::vector<gm_solver*> ss, gm_result* out) {
   gm_solver* s0 = ss[0];
   const int W = s0->world;
   const uint32_t T = s0->rg.T;
-  const bool group = ss.size() > 1;
-  if (group && (int)ss.size() != W) return fail(GM_EINVAL, "group solve needs all %d shards", W);
-  for (size_t i = 0; i < ss.size(); i++) {
-    gm_solver* s = ss[i];
-    if (s->mode != GM_MODE_RANKED || s->world != W || !s->rko_own || (group && s->rank != (int)i))
-      return fail(GM_EINVAL, "ranked md5 shards: ranks 0..%d of one plan", W - 1);
-  }
-  const int mode = group ? 4 : s0->xfer ? 3 : 1;
-  if (mode == 1 && !s0->comm) return fail(GM_EINVAL, "shard %d/%d has no communicator (gm_solver_comm_init)", s0->rank, W);
+  Xchg mode;
+  int rc = xchg_mode(ss, GM_MODE_RANKED, &mode);
+  if (rc) return rc;
+  for (gm_solver* s : ss)
+    if (s->world != W || !s->rko_own) return fail(GM_EINVAL, "ranked md5 shards: ranks 0..%d of one plan", W - 1);
+  // a group orders its shards by events whether or not they share a stream
+  if (mode == XCHG_GROUP) mode = XCHG_STREAMS;
+  const bool group = mode == XCHG_STREAMS;
   SolveEvents ev;  // the solve's events, destroyed on every return
   if (ev.begin()) return GM_EHIP;
   const hipEvent_t e0 = ev.e0, e1 = ev.e1, e2 = ev.e2;
@@ -340,8 +339,11 @@ static int run_ranked_shards(std::vector<gm_solver*> ss, gm_result* out) {
       if (group) HIPCHK(hipEventRecord(PE[i], s->stream));
     }
     HIPCHK(hipGetLastError());
-    // every rank's pack to every other
-    if (mode == 4) {
+    // every rank's pack to every other.  A group keeps its own copy loop, not
+    // xchg_copies: the sizes are replicated (nothing to check), and a sender
+    // is released a level later, before its next pack (CE above), so the
+    // unpack below does not wait for the other receivers
+    if (group) {
       for (size_t i = 0; i < ss.size(); i++) {
         gm_solver* t = ss[i];
         for (size_t j = 0; j < ss.size(); j++) {
@@ -354,32 +356,15 @@ static int run_ranked_shards(std::vector<gm_solver*> ss, gm_result* out) {
         }
         HIPCHK(hipEventRecord(CE[i], t->stream));
       }
-    } else if (mode == 1) {
+    } else {  // this rank's pack to every other, every other's into its part of the receive buffer
       gm_solver* s = s0;
-      RCCL_LIVE(s);
-      ncclGroupStart();
-      ncclResult_t r = ncclSuccess;
-      for (int p = 0; p < W && r == ncclSuccess; p++) {
+      XLists x;
+      for (int p = 0; p < W; p++) {
         if (p == s->rank) continue;
-        const u64 ns = s->rko_tot_h[(size_t)L * W + s->rank], nr = s->rko_tot_h[(size_t)L * W + p];
-        if (ns) r = ncclSend(s->rko_pk, ns, ncclUint8, p, s->comm, s->stream);
-        if (nr && r == ncclSuccess)
-          r = ncclRecv(s->rko_rb + rko_roff(s, L, s->rank, p), nr, ncclUint8, p, s->comm, s->stream);
+        x.out.push_back({p, s->rko_pk, s->rko_tot_h[(size_t)L * W + s->rank]});
+        x.in.push_back({p, s->rko_rb + rko_roff(s, L, s->rank, p), s->rko_tot_h[(size_t)L * W + p]});
       }
-      const ncclResult_t r2 = ncclGroupEnd();
-      if (r != ncclSuccess || r2 != ncclSuccess)
-        return fail(GM_EHIP, "RCCL level exchange: %s", ncclGetErrorString(r != ncclSuccess ? r : r2));
-    } else {  // mode 3: pairwise rounds, send to rank + d, receive from rank - d
-      gm_solver* s = s0;
-      for (int dd = 1; dd < W; dd++) {
-        const int sp = (s->rank + dd) % W, rp = (s->rank - dd + W) % W;
-        std::vector<HostRange> o, in;
-        const u64 ns = s->rko_tot_h[(size_t)L * W + s->rank], nr = s->rko_tot_h[(size_t)L * W + rp];
-        if (ns) o.push_back({s->rko_pk, ns});
-        if (nr) in.push_back({s->rko_rb + rko_roff(s, L, s->rank, rp), nr});
-        int rc = xfer_ranges(s, o, sp, in, rp, s->stream);
-        if (rc) return rc;
-      }
+      if ((rc = xchg_ranges(s, mode, s->stream, x, xchg_rounds(s->rank, W), "level exchange"))) return rc;
     }
     for (gm_solver* s : ss) {
       if (!nt) continue;
@@ -400,15 +385,7 @@ static int run_ranked_shards(std::vector<gm_solver*> ss, gm_result* out) {
     if (s->rank != 0) HIPCHK(hipMemsetAsync(&s->st->red[0], 0, sizeof(u64), s->stream));
   }
   HIPCHK(hipGetLastError());
-  if (mode == 1) {
-    RCCL_LIVE(s0);
-    ncclGroupStart();
-    ncclResult_t r = ncclAllReduce(s0->st->red, s0->st->red, 4, ncclUint64, ncclSum, s0->comm, st);
-    ncclResult_t r2 = ncclAllGather(s0->st->red + 4, s0->errg, 1, ncclUint64, s0->comm, st);
-    ncclResult_t r3 = ncclGroupEnd();
-    if (r != ncclSuccess || r2 != ncclSuccess || r3 != ncclSuccess)
-      return fail(GM_EHIP, "RCCL allreduce: %s", ncclGetErrorString(r != ncclSuccess ? r : r2 != ncclSuccess ? r2 : r3));
-  }
+  if (mode == XCHG_RCCL && (rc = xchg_reduce_rccl(s0, st))) return rc;
   for (size_t i = 0; i < ss.size(); i++)
     if (ss[i]->stream != st) {
       HIPCHK(hipEventRecord(JE[i], ss[i]->stream));
@@ -420,21 +397,7 @@ static int run_ranked_shards(std::vector<gm_solver*> ss, gm_result* out) {
     u64 r[5];
     HIPCHK(hipMemcpyAsync(r, s->st->red, sizeof r, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (mode == 3) {
-      std::vector<u64> all((size_t)5 * W);
-      int rc = xfer_call(s, GM_XFER_ALLGATHER, r, sizeof r, -1, all.data(), all.size() * 8, -1);
-      if (rc) return rc;
-      for (int q = 0; q < W; q++)
-        for (int i = 0; i < 5; i++) red[i] = (i == 4) ? (red[i] | all[(size_t)q * 5 + i]) : red[i] + all[(size_t)q * 5 + i];
-      continue;
-    }
-    if (mode == 1) {
-      std::vector<u64> e((size_t)W);
-      HIPCHK(hipMemcpy(e.data(), s->errg, e.size() * sizeof(u64), hipMemcpyDeviceToHost));
-      r[4] = 0;
-      for (u64 x : e) r[4] |= x;
-    }
-    for (int i = 0; i < 5; i++) red[i] = (i == 4) ? (red[i] | r[i]) : red[i] + r[i];
+    if ((rc = xchg_reduce_fold(s, mode, r, red))) return rc;
   }
   float f = 0, b = 0;
   HIPCHK(hipEventElapsedTime(&f, e0, e1));

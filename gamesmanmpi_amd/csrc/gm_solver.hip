@@ -13,6 +13,9 @@
 //   gm_bucketed.h        BUCKETED kernels
 //   (here)               checksum kernels, struct gm_solver, the HASHED host
 //                        path (run_hashed), the codec C-ABI, k_fill_red
+//   gm_xchg.h            the shards' exchange layer: transport modes and group
+//                        checks, all-gather, ranged send / receive, the
+//                        end-of-solve reduction (no kernels)
 //   gm_dense_run.h       DENSE host path: setup, launches, halo exchanges,
 //                        run_dense (no kernels)
 //   gm_plane_run.h       PLANES host path and its late kernels
@@ -168,14 +171,6 @@ struct PlaneSlot {
   double t_enq = 0;  // host clock at enqueue (ms)
   bool lite = false;  // only ev[0] and ev[3] recorded (a queued one-launch solve)
 };
-
-// an in-process multi-GPU group aborted (solve_multi's abort_all): no RCCL
-// call may use the aborted communicators
-#define RCCL_LIVE(S)                                                                              \
-  do {                                                                                            \
-    if ((S)->gabort && (S)->gabort->load(std::memory_order_acquire))                              \
-      return fail(GM_EHIP, "RCCL group aborted: a peer shard failed (shard %d/%d)", (S)->rank, (S)->world); \
-  } while (0)
 
 enum : uint32_t {
   ERR_TABLE_FULL = 1u,
@@ -1568,6 +1563,7 @@ __device__ __forceinline__ void fill_red_body(DevState* st, const BlockCount* bc
 __global__ __launch_bounds__(1024) void k_fill_red(DevState* st, const BlockCount* bc) { fill_red_body(st, bc); }
 
 // the layouts' host paths (and the kernels that need DevState / gm_solver)
+#include "gm_xchg.h"
 #include "gm_dense_run.h"
 #include "gm_plane_run.h"
 #include "gm_ranked.h"
