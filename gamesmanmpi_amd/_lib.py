@@ -53,6 +53,8 @@ MODE_NAMES = {0: "hashed", 1: "dense", 2: "bucketed", 3: "planes", 4: "ranked"}
 GM_MAXCHILD = 32
 GM_COMM_ID_BYTES = 128
 GM_NO_WORD = 0xFFFFFFFF
+GM_EMPTY_KEY = 0xFFFFFFFFFFFFFFFF
+GM_CENSUS_GENERIC = 1  # gm_solver_census `how`: enumerator + query path on every layout
 
 
 class GmError(RuntimeError):
@@ -117,7 +119,7 @@ EXPORTS = (
     "gm_game_lookup", "gm_game_info", "gm_root", "gm_encode", "gm_decode",
     "gm_encode_batch", "gm_decode_batch", "gm_str_utf8", "gm_host_expand", "gm_host_level", "gm_symmetry", "gm_abi_sizes", "gm_plan", "gm_solver_create",
     "gm_solver_solve", "gm_solver_solve_async", "gm_solver_collect", "gm_solver_query", "gm_solver_positions",
-    "gm_solver_checksum", "gm_solver_moves", "gm_solver_line", "gm_solver_audit",
+    "gm_solver_checksum", "gm_solver_moves", "gm_solver_line", "gm_solver_audit", "gm_solver_census",
     "gm_solver_destroy", "gm_solve", "gm_plan_multi", "gm_query", "gm_release", "gm_owner", "gm_owner_host",
     "gm_plan_shard", "gm_plan_keyed_shard", "gm_solver_create_shard", "gm_comm_unique_id",
     "gm_solver_comm_init", "gm_solve_group", "gm_solver_set_flags", "gm_solver_set_steps",
@@ -177,6 +179,8 @@ def load():
         "gm_solver_line": [c.c_void_p, c.c_uint64, c.c_void_p, c.c_void_p,
                            c.c_uint64, P(c.c_uint64)],
         "gm_solver_audit": [c.c_void_p, c.c_void_p, c.c_uint64, c.c_void_p],
+        "gm_solver_census": [c.c_void_p, c.c_uint32, c.c_void_p, c.c_uint32, c.c_void_p, c.c_uint32,
+                             c.c_void_p],
         "gm_solve": [c.c_int, c.c_uint64, c.c_int, P(gm_buffers),
                      P(gm_result)],
         "gm_plan_multi": [c.c_int, c.c_int, c.c_uint64, c.c_uint32, c.c_uint64, P(gm_plan_t)],

@@ -24,6 +24,7 @@
 //   gm_bucketed_shard.h  md5-sharded BUCKETED levels
 //   (here)               the C-ABI over the layouts: plans, creation, solves
 //   gm_moves.h           move analysis and the table audit
+//   gm_census.h          the census by value, remoteness and level
 //   (here)               readers, gm_solve, gm_ks_*, the explicit-graph solve
 //
 // The HASHED pipeline (this file) replaces the reference's asynchronous
@@ -1158,6 +1159,7 @@ struct gm_solver {
   std::vector<uint32_t> rlvoff;        // per level: first entry of its block list
   std::vector<u64> rlvstart, rlvitems;  // per level: first slot, slots
   u64* rlv_dev = nullptr;              // device: rlvstart then rlvoff (k_rk_scan)
+  u64* cen_dev = nullptr;              // device: gm_solver_census' counts, maxima and witnesses (gm_census.h)
   // md5 shards of the RANKED layout (gm_ranked_shard.h), inside the table
   // buffer: every slot's owner, the level pack / receive buffers, per-level
   // tile counts, their offsets and totals (device; the totals also on the host)
@@ -1921,6 +1923,7 @@ void gm_solver_destroy(gm_solver* s) {
   if (s->errg) (void)hipFree(s->errg);
   if (s->xdev) (void)hipFree(s->xdev);
   if (s->rlv_dev) (void)hipFree(s->rlv_dev);
+  if (s->cen_dev) (void)hipFree(s->cen_dev);
   if (s->own_stream) (void)hipStreamDestroy(s->stream);
   delete s;
 }
@@ -2014,6 +2017,19 @@ int gm_solver_audit(gm_solver* s, uint64_t* bad_keys_dev, uint64_t cap, uint64_t
   const int rc = moves_ready(s, "gm_solver_audit");
   if (rc) return rc;
   return audit_run(s, bad_keys_dev, cap, out);
+}
+
+#include "gm_census.h"
+
+int gm_solver_census(gm_solver* s, uint32_t how, uint64_t* by_rem_dev, uint32_t rem_bins, uint64_t* by_level_dev,
+                     uint32_t levels, uint64_t extremes[12]) {
+  if (!s || !by_rem_dev || (how & ~GM_CENSUS_GENERIC) || (!by_level_dev && levels) || rem_bins == 0xFFFFFFFFu)
+    return fail(GM_EINVAL, "bad argument");
+  const int rc = moves_ready(s, "gm_solver_census");
+  if (rc) return rc;
+  if (by_level_dev && levels < (uint32_t)s->d.max_levels)
+    return fail(GM_EINVAL, "gm_solver_census: %u level rows, the game has %d", levels, s->d.max_levels);
+  return census_run(s, how, by_rem_dev, rem_bins, by_level_dev, levels, extremes);
 }
 
 int gm_solver_query(gm_solver* s, const uint64_t* keys_dev, uint64_t n, uint32_t* words_dev) {

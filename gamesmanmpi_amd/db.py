@@ -20,7 +20,15 @@ files without a descriptor) by str(position).
 adds, under each position, one row per legal move (the module's gen_moves /
 do_move) with the child's value and remoteness from the table, the best move
 marked with `*` (best_index below; the rule of gm_solver_moves,
-include/gamesman.h).  Host only: no GPU is touched.
+include/gamesman.h).
+
+    python -m gamesmanmpi_amd.db DIR --game GAME_FILE --census
+
+prints the analysis table of the whole solution instead: positions by
+remoteness x (Win Lose Tie Draw Total), then by level x the same
+(census_of / format_census below; the launcher's --census prints the same
+tables from the device's gm_solver_census).  Graph tables have no level
+function and print the remoteness table only.  Host only: no GPU is touched.
 """
 import argparse
 import ast
@@ -118,6 +126,64 @@ def best_index(children):
     return min((-r, i) for i, (v, r) in enumerate(children))[1]
 
 
+def census_of(value, remoteness, levels=None, rem_bins=None):
+    """The census of a table held on the host, in gm_solver_census' layout:
+    dict with by_remoteness (uint64 [rem_bins + 1, 4]: positions of remoteness
+    r and value WIN / LOSS / TIE / DRAW, the last row every remoteness >=
+    rem_bins) and by_level (uint64 [max level + 1, 4], or None without
+    `levels`, the level of each position).  rem_bins defaults to the largest
+    remoteness + 1, which leaves the overflow row empty."""
+    value = np.asarray(value).astype(np.int64)
+    remoteness = np.asarray(remoteness).astype(np.int64)
+    if rem_bins is None:
+        rem_bins = int(remoteness.max()) + 1 if len(remoteness) else 0
+    by_rem = np.zeros((int(rem_bins) + 1, 4), np.uint64)
+    np.add.at(by_rem, (np.minimum(remoteness, int(rem_bins)), value), 1)
+    by_lev = None
+    if levels is not None:
+        levels = np.asarray(levels).astype(np.int64)
+        by_lev = np.zeros((int(levels.max()) + 1 if len(levels) else 0, 4), np.uint64)
+        np.add.at(by_lev, (levels, value), 1)
+    return {"by_remoteness": by_rem, "by_level": by_lev}
+
+
+def _census_table(title, rows, overflow=None):
+    """One table: non-empty rows of `rows` ([n, 4]), then the totals.
+    overflow: the index of a last row that collects everything from there on."""
+    rows = np.asarray(rows).astype(np.uint64)
+    fmt = "%12s" + " %14s" * 5
+    out = [fmt % (title, "Win", "Lose", "Tie", "Draw", "Total")]
+    for i, row in enumerate(rows.tolist()):
+        if sum(row):
+            label = ">=%d" % i if i == overflow else "%d" % i
+            out.append(fmt % ((label,) + tuple(row) + (sum(row),)))
+    tot = [int(x) for x in rows.sum(axis=0, dtype=np.uint64)] if len(rows) else [0] * 4
+    out.append(fmt % (("Total",) + tuple(tot) + (sum(tot),)))
+    return out
+
+
+def format_census(by_remoteness, by_level=None):
+    """The analysis table as text: remoteness x (Win Lose Tie Draw Total),
+    non-empty rows only, with a totals line; then, with by_level, level x the
+    same.  The last row of by_remoteness is the overflow row (census_of)."""
+    lines = _census_table("Remoteness", by_remoteness, overflow=len(by_remoteness) - 1)
+    if by_level is not None:
+        lines.append("")
+        lines.extend(_census_table("Level", by_level))
+    return "\n".join(lines)
+
+
+def db_census(db, spec=None, rem_bins=None):
+    """census_of a SolutionDB: keyed tables get their levels from
+    GameSpec.host_level, graph tables (by name) have none."""
+    levels = None
+    if db.by == "key":
+        if spec is None:
+            raise ValueError("a keyed table needs the game's GameSpec")
+        levels = spec.host_level(db.keys)
+    return census_of(db.value, db.remoteness, levels, rem_bins)
+
+
 def position_moves(db, mod, pos, spec=None):
     """[(move, child position, (value, remoteness) or None)] for every legal
     move of a non-primitive position, in gen_moves order."""
@@ -139,6 +205,12 @@ def main(argv=None):
     ap.add_argument("--moves", action="store_true",
                     help="list every legal move of each position with the child's "
                          "value and remoteness; `*` marks the best move")
+    ap.add_argument("--census", action="store_true",
+                    help="print the whole solution's positions by remoteness and by level "
+                         "(Win Lose Tie Draw Total per row) instead of looking positions up")
+    ap.add_argument("--rem-bins", type=int, default=None, metavar="N",
+                    help="--census: remoteness rows 0..N-1, then one row for the rest "
+                         "(default: every remoteness its own row)")
     ap.add_argument("positions", nargs="*")
     args = ap.parse_intermixed_args(argv)
     from . import _lib
@@ -150,6 +222,10 @@ def main(argv=None):
     if db.by == "key":
         from .games import spec_for_module
         spec = spec_for_module(mod, os.path.splitext(os.path.basename(args.game))[0])
+    if args.census:
+        c = db_census(db, spec, args.rem_bins)
+        print(format_census(c["by_remoteness"], c["by_level"]))
+        return 0
     todo = [ast.literal_eval(p) for p in args.positions] or [mod.initial_position()]
     rc = 0
     for pos in todo:

@@ -381,6 +381,41 @@ class Solver:
                 "mismatches": int(out[2]),
                 "bad_keys": bad[:int(out[3])].cpu().numpy().view(np.uint64)}
 
+    def census(self, rem_bins=None, generic=False, levels=True, extremes=True):
+        """Positions by value and remoteness, by value and level, and the
+        hardest position of each value (gm_solver_census), without copying
+        the table: dict with by_remoteness (uint64 [rem_bins + 1, 4], columns
+        WIN LOSS TIE DRAW, the last row every remoteness >= rem_bins),
+        by_level (uint64 [max_levels, 4]) and extremes, per value a dict with
+        count, max_remoteness and key (the smallest key of that value and
+        remoteness; None when the value has no position).  rem_bins defaults
+        to min(max_levels + 1, 65536): every move advances at least one level,
+        so no remoteness exceeds the levels.  generic=True counts through the
+        position enumerator and the query path on every layout.  levels=False
+        / extremes=False leave that part out (by_level / extremes are None)."""
+        torch = self.torch
+        nlev = int(self.plan.max_levels)
+        rem_bins = min(nlev + 1, 65536) if rem_bins is None else int(rem_bins)
+        if not 0 <= rem_bins < 0xFFFFFFFF:
+            raise ValueError("rem_bins must be in [0, 2^32 - 1)")
+        rd = torch.empty((rem_bins + 1, 4), dtype=torch.int64, device=self.device)
+        ld = torch.empty((nlev, 4), dtype=torch.int64, device=self.device) if levels else None
+        ex = np.zeros(12, np.uint64) if extremes else None
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().gm_solver_census(
+                self._h, _lib.GM_CENSUS_GENERIC if generic else 0, rd.data_ptr(), rem_bins,
+                ld.data_ptr() if levels else None, nlev if levels else 0,
+                ex.ctypes.data if extremes else None))
+        out = {"by_remoteness": rd.cpu().numpy().view(np.uint64),
+               "by_level": ld.cpu().numpy().view(np.uint64) if levels else None,
+               "extremes": None}
+        if extremes:
+            out["extremes"] = [
+                {"count": int(ex[3 * v]), "max_remoteness": int(ex[3 * v + 1]),
+                 "key": None if int(ex[3 * v + 2]) == _lib.GM_EMPTY_KEY else int(ex[3 * v + 2])}
+                for v in range(4)]
+        return out
+
     def dump(self):
         """(keys u64, value u8, remoteness u32) for every reachable
         position."""

@@ -113,20 +113,27 @@ def build_parser():
     p.add_argument("--line", action="store_true",
                    help="one-GPU descriptor solves: print the optimal line from the "
                         "initial position, one `position: VALUE in r moves` row per ply")
+    p.add_argument("--census", action="store_true",
+                   help="one-GPU solves: after the solve, print the positions by remoteness "
+                        "and by level (Win Lose Tie Draw Total per row; Solver.census) and "
+                        "the longest win / loss / tie; with --json, a `census` object too")
     return p
 
 
 def check_analysis_args(args, world, descriptor=True):
-    """--audit / --line read one whole table through its device descriptor:
-    a multi-rank run's tables are shards, a graph solve has no descriptor."""
-    asked = [f for f in ("audit", "line") if getattr(args, f)]
+    """--audit / --line / --census read one whole table: a multi-rank run's
+    tables are shards.  --audit / --line go through the device descriptor,
+    which a graph solve does not have (its census is taken on the host)."""
+    asked = [f for f in ("audit", "line", "census") if getattr(args, f)]
     if not asked:
         return
     flags = " / ".join("--" + f for f in asked)
     if world > 1:
         raise SystemExit("%s: one-GPU solves only (%d ranks: every rank's table is a shard)"
                          % (flags, world))
-    if not descriptor or args.layout == "graph":
+    asked = [f for f in asked if f != "census"]
+    flags = " / ".join("--" + f for f in asked)
+    if asked and (not descriptor or args.layout == "graph"):
         raise SystemExit("%s: the game file needs a device descriptor (graph solves are not covered)"
                          % flags)
 
@@ -145,6 +152,51 @@ def run_audit(solver):
     print("audit: %d positions, %d edges, %d mismatches"
           % (a["positions"], a["edges"], a["mismatches"]), flush=True)
     return 1 if a["mismatches"] else 0
+
+
+def census_report(by_remoteness, by_level, witnesses):
+    """(text, json object) of a census: db.format_census' tables, one
+    `longest <VALUE>: <position> in <r> moves` line per non-empty value, and
+    the same as lists.  witnesses: per value (count, max remoteness, position
+    or None)."""
+    from gamesmanmpi_amd.db import NAMES, format_census
+    lines = [format_census(by_remoteness, by_level)]
+    wit = []
+    for v, (count, rem, pos) in enumerate(witnesses):
+        if count:
+            lines.append("longest %s: %s in %d moves" % (NAMES[v], pos, rem))
+        wit.append({"value": NAMES[v], "count": int(count), "max_remoteness": int(rem),
+                    "position": None if not count else str(pos)})
+    obj = {"by_remoteness": by_remoteness.tolist(),
+           "by_level": None if by_level is None else by_level.tolist(),
+           "witnesses": wit}
+    return "\n".join(lines), obj
+
+
+def device_census(spec, solver):
+    """census_report of a descriptor solve, counted on the device."""
+    c = solver.census()
+    wit = [(e["count"], e["max_remoteness"], None if e["key"] is None else spec.pos_of(e["key"]))
+           for e in c["extremes"]]
+    return census_report(c["by_remoteness"], c["by_level"], wit)
+
+
+def host_census(names, value, remoteness):
+    """census_report of a graph solve (no descriptor, hence no levels), from
+    the solved words on the host; the witness is the first name in str order."""
+    import numpy as np
+    from gamesmanmpi_amd.db import census_of
+    c = census_of(value, remoteness)
+    wit = []
+    for v in range(4):
+        m = value == v
+        if not m.any():
+            wit.append((0, 0, None))
+            continue
+        top = int(remoteness[m].max())
+        at = np.nonzero(m & (remoteness == top))[0]
+        wit.append((int(m.sum()), top, min(str(names[i]) for i in at)))
+    return census_report(c["by_remoteness"], None, wit)
 
 
 DENSE_STEMS = ("four_to_one", "sum_four_to_one")  # rank-indexable descriptors
@@ -224,14 +276,20 @@ def solve_generic(args, game, rank, world, local):
         torch.cuda.set_device(local)
         result, solver = solve_module(game, device="cuda:%d" % local)
         print(result.root_line, flush=True)  # src/process.py:47-52
+        census = host_census(*solver.dump()) if args.census else None
         if args.json:
-            print(json.dumps({"game": os.path.basename(args.game_file),
-                              "root": result.root_line,
-                              "positions": result.positions,
-                              "edges": result.edges,
-                              "ms_total": result.ms_total,
-                              "host_enumeration_s": result.extra["host_enumeration_s"],
-                              "layout": "graph", "ranks": 1}), flush=True)
+            row = {"game": os.path.basename(args.game_file),
+                   "root": result.root_line,
+                   "positions": result.positions,
+                   "edges": result.edges,
+                   "ms_total": result.ms_total,
+                   "host_enumeration_s": result.extra["host_enumeration_s"],
+                   "layout": "graph", "ranks": 1}
+            if census:
+                row["census"] = census[1]
+            print(json.dumps(row), flush=True)
+        if census:
+            print(census[0], flush=True)
         if args.statsdir:
             import numpy as np
             d = os.path.join(args.statsdir, "stats", "0")
@@ -356,14 +414,20 @@ def main(argv=None):
         result = solver.solve()
     if rank == 0:
         print(result.root_line, flush=True)  # src/process.py:47-52
+        census = device_census(spec, solver) if args.census else None
         if args.json:
-            print(json.dumps({"game": spec.name, "params": spec.params,
-                              "root": result.root_line,
-                              "positions": result.positions,
-                              "edges": result.edges,
-                              "ms_total": result.ms_total,
-                              "layout": result.extra.get("layout"),
-                              "ranks": world}), flush=True)
+            row = {"game": spec.name, "params": spec.params,
+                   "root": result.root_line,
+                   "positions": result.positions,
+                   "edges": result.edges,
+                   "ms_total": result.ms_total,
+                   "layout": result.extra.get("layout"),
+                   "ranks": world}
+            if census:
+                row["census"] = census[1]
+            print(json.dumps(row), flush=True)
+        if census:
+            print(census[0], flush=True)
     if args.statsdir:
         write_stats(args.statsdir, rank, spec, solver, result, world)
     rc = 0

@@ -323,6 +323,37 @@ int gm_solver_line(gm_solver *s, uint64_t key, uint64_t *keys_dev,
  * to bad_keys_dev (the first `cap` found, in no order; cap may be 0). */
 int gm_solver_audit(gm_solver *s, uint64_t *bad_keys_dev, uint64_t cap,
                     uint64_t out[4]);
+/* The census of a finished solve: how many positions are WIN / LOSS / TIE /
+ * DRAW at each remoteness and at each level (tier), and the hardest position
+ * of each value -- the analysis table a reference user builds by walking the
+ * resolved / remote shelves by hand (src/cache_dict.py:44-79).  Synchronous
+ * on the solver's stream, reads the table only, and serves the solvers the
+ * move analysis serves: GM_EINVAL for a shard (world > 1) and for a solver
+ * that has not solved, or stopped early.  PLANES and RANKED tables are
+ * counted in storage order by kernels of their own (no key, no lookup);
+ * how = GM_CENSUS_GENERIC counts them, as every other layout, through the
+ * position enumerator and the query path (A/B runs, tests).  A reachable
+ * position without a word: GM_ECORRUPT.
+ *   by_rem_dev    device, (rem_bins + 1) * 4 u64, zeroed by the call:
+ *                 by_rem[r * 4 + v] = positions of value v (GM_WIN..GM_DRAW)
+ *                 and remoteness r < rem_bins; row rem_bins = every position
+ *                 of remoteness >= rem_bins (rem_bins may be 0), so the rows
+ *                 add up to the position count
+ *   by_level_dev  device, levels * 4 u64, zeroed by the call: by_level[L * 4
+ *                 + v] = positions of value v whose level (gm_host_level) is
+ *                 L; levels >= the game's max_levels, else GM_EINVAL; NULL
+ *                 with levels = 0 skips the table
+ *   extremes      host, may be NULL; per value v: extremes[3v] = positions of
+ *                 value v, [3v + 1] = the largest remoteness among them
+ *                 (exact also beyond rem_bins), [3v + 2] = the smallest key
+ *                 of that value and remoteness (a second pass over the table,
+ *                 skipped when extremes is NULL); no position of value v:
+ *                 0, 0, GM_EMPTY_KEY */
+#define GM_CENSUS_GENERIC 1u
+int gm_solver_census(gm_solver *s, uint32_t how,
+                     uint64_t *by_rem_dev, uint32_t rem_bins,
+                     uint64_t *by_level_dev, uint32_t levels,
+                     uint64_t extremes[12]);
 /* change GM_F_* flags of an existing solver (e.g. kernel timing) */
 int gm_solver_set_flags(gm_solver *s, uint32_t flags);
 /* Level-granular stop / resume (checkpoints; SURVEY.md §8f rank 2 -- the
