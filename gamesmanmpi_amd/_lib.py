@@ -55,6 +55,9 @@ GM_COMM_ID_BYTES = 128
 GM_NO_WORD = 0xFFFFFFFF
 GM_EMPTY_KEY = 0xFFFFFFFFFFFFFFFF
 GM_CENSUS_GENERIC = 1  # gm_solver_census `how`: enumerator + query path on every layout
+GM_EXPORT_GENERIC = 1  # gm_solver_export `how`: index -> key -> query path on every layout
+GM_NO_INDEX = 0xFFFFFFFFFFFFFFFF  # gm_tb_index: the key is no position of the game
+GM_TB_BLOCK = 512  # tablebase indexes per block
 
 
 class GmError(RuntimeError):
@@ -127,6 +130,7 @@ EXPORTS = (
     "gm_ks_begin", "gm_ks_level_size", "gm_ks_expand", "gm_ks_insert",
     "gm_ks_finalize", "gm_ks_counts", "gm_ks_children", "gm_ks_reduce",
     "gm_ks_end", "gm_graph_solve",
+    "gm_tb_info", "gm_tb_index", "gm_solver_export",
     "gm_last_error", "gm_version",
 )
 
@@ -181,6 +185,10 @@ def load():
         "gm_solver_audit": [c.c_void_p, c.c_void_p, c.c_uint64, c.c_void_p],
         "gm_solver_census": [c.c_void_p, c.c_uint32, c.c_void_p, c.c_uint32, c.c_void_p, c.c_uint32,
                              c.c_void_p],
+        "gm_tb_info": [c.c_int, P(c.c_uint64)],
+        "gm_tb_index": [c.c_int, c.c_void_p, c.c_size_t, c.c_void_p],
+        "gm_solver_export": [c.c_void_p, c.c_uint32, c.c_uint64, c.c_uint64, c.c_uint32, c.c_void_p,
+                             c.c_void_p, c.c_void_p, c.c_uint64, P(c.c_uint64)],
         "gm_solve": [c.c_int, c.c_uint64, c.c_int, P(gm_buffers),
                      P(gm_result)],
         "gm_plan_multi": [c.c_int, c.c_int, c.c_uint64, c.c_uint32, c.c_uint64, P(gm_plan_t)],

@@ -68,7 +68,7 @@ __device__ __forceinline__ void rk_unpack(const RankGeom& g, uint32_t ph, RankPo
 struct RankHands {
   int t1, o1, t2, o2;
 };
-__device__ __forceinline__ RankHands rk_hands(uint32_t L, uint32_t nT, uint32_t a) {
+GM_HD RankHands rk_hands(uint32_t L, uint32_t nT, uint32_t a) {
   RankHands u;
   u.t1 = (int)a;
   u.o1 = (int)((L + 1) / 2) - (int)a;
@@ -76,7 +76,7 @@ __device__ __forceinline__ RankHands rk_hands(uint32_t L, uint32_t nT, uint32_t 
   u.o2 = (int)(L / 2) - u.t2;
   return u;
 }
-__device__ __forceinline__ bool rk_valid(const RankHands& u) {
+GM_HD bool rk_valid(const RankHands& u) {
   return u.t1 >= 0 && u.t1 <= (int)kRankHand && u.o1 >= 0 && u.o1 <= (int)kRankHand && u.t2 >= 0 &&
          u.t2 <= (int)kRankHand && u.o2 >= 0 && u.o2 <= (int)kRankHand;
 }
@@ -100,8 +100,10 @@ __device__ __forceinline__ u64 rk_key(const RankGeom& g, const RankPos& p, uint3
          ((u64)(kRankHand - u.t1) << (2 * A + 6)) | ((u64)(kRankHand - u.o1) << (2 * A + 9)) |
          ((u64)(L & 1u) << (2 * A + 12));
 }
-// key -> slot (false: not a gravity board with consistent hands)
-__device__ __forceinline__ bool rk_slot_of(const RankGeom& g, u64 key, u64* slot, uint32_t* level) {
+// key -> slot (false: not a gravity board with consistent hands).  Host and
+// device share this body: on the host g.base is rank_shape's table
+// (gm_tb_index), on the device the table buffer's copy of it.
+GM_HD bool rk_slot_of(const RankGeom& g, u64 key, u64* slot, uint32_t* level) {
   const uint32_t A = g.A;
   const u64 full = (A >= 64) ? ~0ull : ((1ull << A) - 1);
   const u64 t = key & full, o = (key >> A) & full;

@@ -1160,6 +1160,13 @@ struct gm_solver {
   std::vector<u64> rlvstart, rlvitems;  // per level: first slot, slots
   u64* rlv_dev = nullptr;              // device: rlvstart then rlvoff (k_rk_scan)
   u64* cen_dev = nullptr;              // device: gm_solver_census' counts, maxima and witnesses (gm_census.h)
+  // gm_solver_export (gm_export.h): block offsets and totals of a call (device,
+  // grown on demand); for toot tables of the keyed layouts the level tables
+  // and packed heights of the RANKED index map (xg.lvph, the lvt halves)
+  u64* exp_dev = nullptr;
+  size_t exp_words = 0;
+  u64* xgeo_dev = nullptr;
+  RankGeom xg{};
   // md5 shards of the RANKED layout (gm_ranked_shard.h), inside the table
   // buffer: every slot's owner, the level pack / receive buffers, per-level
   // tile counts, their offsets and totals (device; the totals also on the host)
@@ -1924,6 +1931,8 @@ void gm_solver_destroy(gm_solver* s) {
   if (s->xdev) (void)hipFree(s->xdev);
   if (s->rlv_dev) (void)hipFree(s->rlv_dev);
   if (s->cen_dev) (void)hipFree(s->cen_dev);
+  if (s->exp_dev) (void)hipFree(s->exp_dev);
+  if (s->xgeo_dev) (void)hipFree(s->xgeo_dev);
   if (s->own_stream) (void)hipStreamDestroy(s->stream);
   delete s;
 }
@@ -2030,6 +2039,57 @@ int gm_solver_census(gm_solver* s, uint32_t how, uint64_t* by_rem_dev, uint32_t 
   if (by_level_dev && levels < (uint32_t)s->d.max_levels)
     return fail(GM_EINVAL, "gm_solver_census: %u level rows, the game has %d", levels, s->d.max_levels);
   return census_run(s, how, by_rem_dev, rem_bins, by_level_dev, levels, extremes);
+}
+
+#include "gm_export.h"
+
+int gm_tb_info(int game, uint64_t* index_space) {
+  const Desc* d = get_game(game);
+  if (!d || !index_space) return fail(GM_EINVAL, "bad argument");
+  u64 space = 0;
+  const int rc = tb_space(d, &space, nullptr);
+  if (!rc) *index_space = space;
+  return rc;
+}
+
+int gm_tb_index(int game, const uint64_t* keys, size_t n, uint64_t* index) {
+  const Desc* d = get_game(game);
+  if (!d || (n && (!keys || !index))) return fail(GM_EINVAL, "bad argument");
+  u64 space;
+  RankShape rs;
+  const int rc = tb_space(d, &space, &rs);
+  if (rc) return rc;
+  if (d->kind == K_SUM) {
+    const u64 total = tb_sum_total(d);
+    for (size_t i = 0; i < n; i++) index[i] = keys[i] < total ? keys[i] : GM_NO_INDEX;
+    return 0;
+  }
+  rs.g.base = rs.base.data();  // (the host's copy: rk_slot_of reads nothing else through a pointer)
+  for (size_t i = 0; i < n; i++) {
+    u64 slot;
+    uint32_t L;
+    index[i] = rk_slot_of(rs.g, keys[i], &slot, &L) ? slot : GM_NO_INDEX;
+  }
+  return 0;
+}
+
+int gm_solver_export(gm_solver* s, uint32_t how, uint64_t first, uint64_t count, uint32_t word_bytes,
+                     uint64_t* bits_dev, uint32_t* block_counts_dev, void* words_dev, uint64_t words_cap,
+                     uint64_t* n_words) {
+  if (!s || !n_words || (how & ~GM_EXPORT_GENERIC) || (word_bytes != 1 && word_bytes != 2 && word_bytes != 4) ||
+      (count && (!bits_dev || !block_counts_dev)) || (words_cap && !words_dev) || (((uintptr_t)words_dev | (uintptr_t)bits_dev) & 15u))
+    return fail(GM_EINVAL, "bad argument");
+  *n_words = 0;
+  int rc = moves_ready(s, "gm_solver_export");
+  if (rc) return rc;
+  u64 space;
+  rc = tb_space(&s->d, &space, nullptr);
+  if (rc) return rc;
+  if (first % GM_TB_BLOCK || count % GM_TB_BLOCK || first > space || count > space - first)
+    return fail(GM_EINVAL, "gm_solver_export: indexes [%llu, +%llu) are no whole blocks of %u inside the index space %llu",
+                (unsigned long long)first, (unsigned long long)count, GM_TB_BLOCK, (unsigned long long)space);
+  if (!count) return 0;
+  return export_run(s, how, first, count, word_bytes, (u64*)bits_dev, block_counts_dev, words_dev, words_cap, n_words);
 }
 
 int gm_solver_query(gm_solver* s, const uint64_t* keys_dev, uint64_t n, uint32_t* words_dev) {

@@ -29,6 +29,17 @@ remoteness x (Win Lose Tie Draw Total), then by level x the same
 (census_of / format_census below; the launcher's --census prints the same
 tables from the device's gm_solver_census).  Graph tables have no level
 function and print the remoteness table only.  Host only: no GPU is touched.
+
+Indexed games (four_to_one, sum_four_to_one, toot_and_otto_bitstring) may be
+saved as an indexed tablebase instead, `<DIR>/stats/0/solution.gmtb` (the
+launcher's `-sd DIR --tablebase`, written on the GPU by
+Solver.export_tablebase; the format and its reader, Tablebase, are below):
+SolutionDB opens it with np.memmap when present and every query above works
+on it unchanged, except that --census prints the remoteness table only.
+
+    python -m gamesmanmpi_amd.db DIR --game GAME_FILE --to-tablebase
+
+converts a directory's solution.npz files to that file (write_tablebase).
 """
 import argparse
 import ast
@@ -41,9 +52,189 @@ import numpy as np
 
 NAMES = ("WIN", "LOSS", "TIE", "DRAW")
 
+# ---------------------------------------------------------------------------
+# the indexed tablebase, solution.gmtb
+# ---------------------------------------------------------------------------
+# A position of an indexed game has an index computed from its key alone
+# (gm_tb_index).  The file holds, little-endian:
+#   header   64 bytes: magic "GMTBASE1", u32 version, u32 word_bytes, then u64
+#            index_space, positions, bitmap offset, counts offset, words
+#            offset, file bytes
+#   bitmap   index_space / 8 bytes: bit i (of u64 i / 64, bit i % 64) = index
+#            i is reached
+#   counts   index_space / 512 + 1 u64: reached indexes before each 512-block
+#   words    positions * word_bytes: value | remoteness << 2 of the reached
+#            indexes, in index order
+# A lookup is one bit test, the block's count plus the popcount of the
+# block's earlier bitmap words, and one load; no keys are stored and nothing
+# is loaded up front.
+TB_MAGIC = b"GMTBASE1"
+TB_VERSION = 1
+TB_HEADER = 64
+TB_BLOCK = 512
+TB_NAME = "solution.gmtb"
+_TB_DTYPES = {1: np.dtype("<u1"), 2: np.dtype("<u2"), 4: np.dtype("<u4")}
+NO_WORD = 0xFFFFFFFF
+NO_INDEX = 0xFFFFFFFFFFFFFFFF
+
+
+def tb_word_bytes(max_remoteness):
+    """Bytes of a compact word (value | remoteness << 2) that hold every
+    remoteness up to max_remoteness."""
+    return 1 if max_remoteness <= 63 else 2 if max_remoteness <= 16383 else 4
+
+
+def tb_header(index_space, word_bytes, positions):
+    """The 64 header bytes and the three section offsets."""
+    if index_space % TB_BLOCK or word_bytes not in _TB_DTYPES:
+        raise ValueError("index space %d / word bytes %d" % (index_space, word_bytes))
+    bits_off = TB_HEADER
+    counts_off = bits_off + index_space // 8
+    words_off = counts_off + 8 * (index_space // TB_BLOCK + 1)
+    total = words_off + positions * word_bytes
+    head = TB_MAGIC + np.array([TB_VERSION, word_bytes], "<u4").tobytes() + np.array(
+        [index_space, positions, bits_off, counts_off, words_off, total], "<u8").tobytes()
+    assert len(head) == TB_HEADER
+    return head, bits_off, counts_off, words_off
+
+
+_POP8 = np.array([bin(i).count("1") for i in range(256)], np.uint8)
+
+
+def _popcount64(x):
+    """Set bits of each uint64 of `x` (any shape), as int64."""
+    x = np.ascontiguousarray(x, dtype="<u8")
+    return _POP8[x.view(np.uint8).reshape(x.shape + (8,))].sum(axis=-1, dtype=np.int64)
+
+
+def write_tablebase(path, index_space, indexes, words, word_bytes):
+    """Write solution.gmtb from (index, word) pairs on the host (pure numpy;
+    the device writer is Solver.export_tablebase).  index_space: gm_tb_info's;
+    words: value | remoteness << 2."""
+    indexes = np.ascontiguousarray(indexes, dtype=np.uint64)
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    if len(indexes) != len(words):
+        raise ValueError("%d indexes, %d words" % (len(indexes), len(words)))
+    order = np.argsort(indexes, kind="stable")
+    indexes, words = indexes[order], words[order]
+    if len(indexes) and int(indexes[-1]) >= index_space:
+        raise ValueError("index %d outside the index space %d" % (int(indexes[-1]), index_space))
+    if len(indexes) > 1 and (np.diff(indexes) == 0).any():
+        raise ValueError("an index appears twice")
+    if word_bytes < 4 and len(words) and int(words.max()) >> (8 * word_bytes):
+        raise ValueError("remoteness %d does not fit words of %d byte(s)" % (int(words.max()) >> 2, word_bytes))
+    head, _, _, _ = tb_header(index_space, word_bytes, len(indexes))
+    reached = np.zeros(index_space, np.uint8)
+    reached[indexes.astype(np.int64)] = 1
+    counts = np.zeros(index_space // TB_BLOCK + 1, "<u8")
+    counts[1:] = np.cumsum(reached.reshape(-1, TB_BLOCK).sum(axis=1, dtype=np.uint64))
+    tmp = path + ".tmp"
+    with open(tmp, "wb") as f:
+        f.write(head)
+        f.write(np.packbits(reached, bitorder="little").tobytes())
+        f.write(counts.tobytes())
+        f.write(words.astype(_TB_DTYPES[word_bytes]).tobytes())
+    os.replace(tmp, path)
+
+
+class Tablebase:
+    """solution.gmtb opened with np.memmap: the three sections are mapped,
+    nothing is read until a lookup touches it.  spec: the game's GameSpec
+    (its gm_tb_index maps keys to indexes)."""
+
+    def __init__(self, path, spec=None):
+        self.path, self.spec = path, spec
+        size = os.path.getsize(path)
+        with open(path, "rb") as f:
+            head = f.read(TB_HEADER)
+        if len(head) < TB_HEADER or head[:8] != TB_MAGIC:
+            raise ValueError("%s is no tablebase (bad magic)" % path)
+        version, wb = (int(x) for x in np.frombuffer(head, "<u4", 2, 8))
+        space, npos, bits_off, counts_off, words_off, total = (int(x) for x in np.frombuffer(head, "<u8", 6, 16))
+        if version != TB_VERSION:
+            raise ValueError("%s: tablebase version %d, this reader knows %d" % (path, version, TB_VERSION))
+        if wb not in _TB_DTYPES or space % TB_BLOCK:
+            raise ValueError("%s: bad header (word bytes %d, index space %d)" % (path, wb, space))
+        want = tb_header(space, wb, npos)
+        if (bits_off, counts_off, words_off) != want[1:] or total != words_off + npos * wb:
+            raise ValueError("%s: section offsets do not match the header's sizes" % path)
+        if size != total:
+            raise ValueError("%s holds %d bytes, its header says %d (truncated?)" % (path, size, total))
+        if spec is not None and spec.tb_index_space() != space:
+            raise ValueError("%s: index space %d, %r has %d" % (path, space, spec, spec.tb_index_space()))
+        self.index_space, self.positions, self.word_bytes = space, npos, wb
+        self.bits = np.memmap(path, "<u8", "r", bits_off, (space // 64,))
+        self.counts = np.memmap(path, "<u8", "r", counts_off, (space // TB_BLOCK + 1,))
+        self.words = (np.memmap(path, _TB_DTYPES[wb], "r", words_off, (npos,)) if npos
+                      else np.zeros(0, _TB_DTYPES[wb]))
+        if int(self.counts[-1]) != npos:  # (one page of the counts: every lookup's bound)
+            raise ValueError("%s: %d reached indexes counted, %d words" % (path, int(self.counts[-1]), npos))
+
+    def __len__(self):
+        return self.positions
+
+    def lookup_indexes(self, indexes):
+        """uint32 words (value | remoteness << 2) of tablebase indexes;
+        NO_WORD for an unreached index, NO_INDEX or an index outside the space."""
+        idx = np.ascontiguousarray(indexes, dtype=np.uint64)
+        out = np.full(len(idx), NO_WORD, np.uint32)
+        ok = idx < np.uint64(self.index_space)
+        if not ok.any():
+            return out
+        i = idx[ok].astype(np.int64)
+        w, b = i >> 6, (i & 63).astype(np.uint64)
+        word = np.asarray(self.bits[w])
+        hit = ((word >> b) & np.uint64(1)).astype(bool)
+        i, w, b, word = i[hit], w[hit], b[hit], word[hit]
+        blk = i >> 9
+        # the block's earlier bitmap words, then the bits below in this word
+        rows = np.asarray(self.bits[(blk[:, None] << 3) + np.arange(8)[None, :]])
+        before = np.arange(8)[None, :] < (w & 7)[:, None]
+        rank = (np.asarray(self.counts[blk]).astype(np.int64) + (_popcount64(rows) * before).sum(axis=1)
+                + _popcount64(word & ((np.uint64(1) << b) - np.uint64(1))))
+        if len(rank) and int(rank.max()) >= self.positions:
+            raise ValueError("%s: the bitmap and the block counts disagree" % self.path)
+        res = np.full(len(hit), NO_WORD, np.uint32)
+        res[hit] = np.asarray(self.words[rank]).astype(np.uint32)
+        out[ok] = res
+        return out
+
+    def lookup_keys(self, keys):
+        """uint32 words of packed u64 keys (NO_WORD: not in the table)."""
+        if self.spec is None:
+            raise ValueError("a tablebase lookup by key needs the game's GameSpec")
+        return self.lookup_indexes(self.spec.tb_index(keys))
+
+    def lookup_key(self, key):
+        w = int(self.lookup_keys(np.array([key], np.uint64))[0])
+        return None if w == NO_WORD else (w & 3, w >> 2)
+
+    def by_remoteness(self, rem_bins=None, chunk=1 << 24):
+        """census_of's by_remoteness table, streamed from the words section."""
+        top = 0
+        for a in range(0, self.positions, chunk):
+            top = max(top, int(np.asarray(self.words[a:a + chunk]).max()) >> 2)
+        if rem_bins is None:
+            rem_bins = top + 1 if self.positions else 0
+        by_rem = np.zeros((int(rem_bins) + 1, 4), np.uint64)
+        for a in range(0, self.positions, chunk):
+            w = np.asarray(self.words[a:a + chunk]).astype(np.int64)
+            np.add.at(by_rem, (np.minimum(w >> 2, int(rem_bins)), w & 3), 1)
+        return by_rem
+
 
 class SolutionDB:
     def __init__(self, root):
+        tb = os.path.join(root, "stats", "0", TB_NAME)
+        if os.path.exists(tb):
+            # an indexed tablebase (one-GPU solves of indexed games): mapped, not loaded
+            with open(os.path.join(os.path.dirname(tb), "meta.json")) as f:
+                self.meta = json.load(f)
+            from .games import GameSpec
+            self.by, self.ranks = "key", 1
+            self.tablebase = Tablebase(tb, GameSpec(self.meta["game"], self.meta.get("params", "")))
+            return
+        self.tablebase = None
         ranks = sorted(glob.glob(os.path.join(root, "stats", "*", "solution.npz")))
         if not ranks:
             raise FileNotFoundError("no stats/<rank>/solution.npz under %r" % root)
@@ -77,9 +268,11 @@ class SolutionDB:
             self.index = {str(n): i for i, n in enumerate(np.concatenate(names))}
 
     def __len__(self):
-        return len(self.value)
+        return len(self.tablebase) if self.tablebase is not None else len(self.value)
 
     def lookup_key(self, key):
+        if self.tablebase is not None:
+            return self.tablebase.lookup_key(key)
         i = int(np.searchsorted(self.keys, np.uint64(key)))
         if i == len(self.keys) or int(self.keys[i]) != int(key):
             return None
@@ -177,6 +370,9 @@ def db_census(db, spec=None, rem_bins=None):
     """census_of a SolutionDB: keyed tables get their levels from
     GameSpec.host_level, graph tables (by name) have none."""
     levels = None
+    if getattr(db, "tablebase", None) is not None:
+        # no inverse index: the remoteness table only, as graph tables
+        return {"by_remoteness": db.tablebase.by_remoteness(rem_bins), "by_level": None}
     if db.by == "key":
         if spec is None:
             raise ValueError("a keyed table needs the game's GameSpec")
@@ -198,6 +394,31 @@ def position_moves(db, mod, pos, spec=None):
     return out
 
 
+def convert_to_tablebase(root, spec):
+    """stats/<rank>/solution.npz of a keyed table of an indexed game ->
+    stats/0/solution.gmtb (+ "format": "gmtb" in its meta.json).  The npz
+    files stay; SolutionDB prefers the tablebase."""
+    db = SolutionDB(root)
+    if db.tablebase is not None:
+        raise ValueError("%r already holds a tablebase" % root)
+    if db.by != "key":
+        raise ValueError("graph tables (by position name) have no index")
+    idx = spec.tb_index(db.keys)
+    if (idx == np.uint64(NO_INDEX)).any():
+        raise ValueError("the table holds keys that are no position of %r" % (spec,))
+    words = db.value.astype(np.uint32) | (db.remoteness.astype(np.uint32) << 2)
+    wb = tb_word_bytes(int(db.remoteness.max()) if len(db) else 0)
+    d = os.path.join(root, "stats", "0")
+    os.makedirs(d, exist_ok=True)
+    meta = dict(db.meta, game=spec.name, params=spec.params, positions=len(db), format="gmtb",
+                word_bytes=wb)
+    meta.pop("owned_by_rank", None)
+    write_tablebase(os.path.join(d, TB_NAME), spec.tb_index_space(), idx, words, wb)
+    with open(os.path.join(d, "meta.json"), "w") as f:
+        json.dump(meta, f, indent=1)
+    return os.path.join(d, TB_NAME)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="gamesmanmpi_amd.db")
     ap.add_argument("statsdir")
@@ -211,12 +432,24 @@ def main(argv=None):
     ap.add_argument("--rem-bins", type=int, default=None, metavar="N",
                     help="--census: remoteness rows 0..N-1, then one row for the rest "
                          "(default: every remoteness its own row)")
+    ap.add_argument("--to-tablebase", action="store_true",
+                    help="convert the directory's solution.npz files to the indexed tablebase "
+                         "stats/0/solution.gmtb (indexed games: four_to_one, sum_four_to_one, "
+                         "toot_and_otto_bitstring) and exit")
     ap.add_argument("positions", nargs="*")
     args = ap.parse_intermixed_args(argv)
     from . import _lib
     from .solver_launcher import ensure_src_utils, load_game
     ensure_src_utils()
     mod = load_game(args.game)
+    if args.to_tablebase:
+        from .games import spec_for_module
+        spec = spec_for_module(mod, os.path.splitext(os.path.basename(args.game))[0])
+        try:
+            print(convert_to_tablebase(args.statsdir, spec))
+        except (ValueError, _lib.GmError) as e:
+            raise SystemExit("--to-tablebase: %s" % e)
+        return 0
     db = SolutionDB(args.statsdir)
     spec = None
     if db.by == "key":

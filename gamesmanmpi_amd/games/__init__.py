@@ -150,6 +150,23 @@ class GameSpec:
                                              len(keys), out.ctypes.data))
         return out
 
+    # -- the tablebase index (include/gamesman.h gm_tb_info / gm_tb_index) --
+    def tb_index_space(self):
+        """Size of the game's tablebase index space (a multiple of 512);
+        GmError for games without an index function."""
+        n = _lib.ctypes.c_uint64()
+        _lib.check(_lib.load().gm_tb_info(self.id, _lib.ctypes.byref(n)))
+        return n.value
+
+    def tb_index(self, keys):
+        """Tablebase index of each key (uint64[n]); GM_NO_INDEX for a key
+        that is no position of the game."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        out = np.zeros(len(keys), np.uint64)
+        _lib.check(_lib.load().gm_tb_index(self.id, keys.ctypes.data,
+                                           len(keys), out.ctypes.data))
+        return out
+
     def owners_host(self, keys, world_size):
         """GameState.get_hash(world_size) (src/game_state.py:22-30)."""
         keys = np.ascontiguousarray(keys, dtype=np.uint64)

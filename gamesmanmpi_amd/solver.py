@@ -416,6 +416,70 @@ class Solver:
                 for v in range(4)]
         return out
 
+    # -- the indexed tablebase (gm_solver_export; db.Tablebase reads it) ------
+    def export_range(self, first, count, word_bytes, generic=False, words_cap=None):
+        """Tablebase sections of indexes [first, first + count) as device
+        tensors (gm_solver_export): (bits int64[count / 64], block_counts
+        int32[count / 512], words uint8[n * word_bytes]).  words_cap: room for
+        that many words (default: one per index); TableFull when short."""
+        torch = self.torch
+        first, count, word_bytes = int(first), int(count), int(word_bytes)
+        cap = count if words_cap is None else int(words_cap)
+        bits = torch.empty(max(1, count // 64), dtype=torch.int64, device=self.device)
+        counts = torch.empty(max(1, count // _lib.GM_TB_BLOCK), dtype=torch.int32, device=self.device)
+        words = torch.empty(max(16, cap * word_bytes), dtype=torch.uint8, device=self.device)
+        n = ctypes.c_uint64()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().gm_solver_export(
+                self._h, _lib.GM_EXPORT_GENERIC if generic else 0, first, count, word_bytes,
+                bits.data_ptr(), counts.data_ptr(), words.data_ptr(), cap, ctypes.byref(n)))
+        return bits[:count // 64], counts[:count // _lib.GM_TB_BLOCK], words[:n.value * word_bytes]
+
+    def export_tablebase(self, path, chunk=1 << 26, generic=False):
+        """Write the finished solve as the indexed tablebase `path`
+        (solution.gmtb, db.Tablebase): the reach bitmap over the game's index
+        space, a cumulative count per 512-index block and one compact word per
+        reached index, all produced on the device `chunk` indexes at a time
+        and streamed to the file through one pinned host buffer -- no keys, no
+        host copy of the table.  The word width comes from the census' largest
+        remoteness.  Returns dict(path, bytes, positions, word_bytes)."""
+        import os
+        from . import db
+        torch = self.torch
+        space = self.spec.tb_index_space()
+        ext = self.census(rem_bins=0, levels=False)["extremes"]
+        wb = db.tb_word_bytes(max(e["max_remoteness"] for e in ext))
+        chunk = max(_lib.GM_TB_BLOCK, int(chunk) // _lib.GM_TB_BLOCK * _lib.GM_TB_BLOCK)
+        _, bits_off, counts_off, words_off = db.tb_header(space, wb, 0)
+        stage = torch.empty(min(chunk, space) * wb, dtype=torch.uint8, pin_memory=True)
+        host = stage.numpy()
+
+        def out(fh, at, t):  # device tensor -> file offset `at`, through the pinned buffer
+            flat = t.view(torch.uint8).reshape(-1)
+            stage[:flat.numel()].copy_(flat)
+            fh.seek(at)
+            fh.write(host[:flat.numel()].data)
+
+        tmp = path + ".tmp"
+        npos = 0
+        with open(tmp, "wb") as fh:
+            fh.write(b"\0" * db.TB_HEADER)
+            fh.seek(counts_off)
+            fh.write(np.zeros(1, "<u8").tobytes())
+            for first in range(0, space, chunk):
+                count = min(chunk, space - first)
+                bits, counts, words = self.export_range(first, count, wb, generic)
+                out(fh, bits_off + first // 8, bits)
+                cum = torch.cumsum(counts.to(torch.int64), 0) + npos
+                out(fh, counts_off + 8 * (first // _lib.GM_TB_BLOCK + 1), cum)
+                if words.numel():
+                    out(fh, words_off + npos * wb, words)
+                npos += words.numel() // wb
+            fh.seek(0)
+            fh.write(db.tb_header(space, wb, npos)[0])
+        os.replace(tmp, path)
+        return {"path": path, "bytes": words_off + npos * wb, "positions": npos, "word_bytes": wb}
+
     def dump(self):
         """(keys u64, value u8, remoteness u32) for every reachable
         position."""

@@ -117,7 +117,44 @@ def build_parser():
                    help="one-GPU solves: after the solve, print the positions by remoteness "
                         "and by level (Win Lose Tie Draw Total per row; Solver.census) and "
                         "the longest win / loss / tie; with --json, a `census` object too")
+    p.add_argument("--tablebase", action="store_true",
+                   help="with -sd, one-GPU solves of indexed games (four_to_one, sum_four_to_one, "
+                        "toot_and_otto_bitstring): write the indexed tablebase solution.gmtb "
+                        "(exported on the GPU, read by mmap: gamesmanmpi_amd.db) instead of "
+                        "solution.npz")
     return p
+
+
+def check_tablebase_args(args, world, spec=None, descriptor=True):
+    """--tablebase writes one table from one GPU, for a game with an index."""
+    if not args.tablebase:
+        return
+    if not args.statsdir:
+        raise SystemExit("--tablebase: needs -sd DIR")
+    if world > 1:
+        raise SystemExit("--tablebase: one-GPU solves only (%d ranks: every rank's table is a shard)" % world)
+    if not descriptor or args.layout == "graph":
+        raise SystemExit("--tablebase: the game file needs a device descriptor (graph solves keep solution.npz)")
+    if spec is not None:
+        from gamesmanmpi_amd import _lib
+        try:
+            spec.tb_index_space()
+        except _lib.GmError:
+            raise SystemExit("--tablebase: %s has no tablebase index (keyed games without a rank function "
+                             "keep solution.npz)" % spec.name)
+
+
+def write_tablebase_stats(statsdir, spec, solver, result):
+    """<statsdir>/stats/0/solution.gmtb (+ meta.json, "format": "gmtb")."""
+    d = os.path.join(statsdir, "stats", "0")
+    os.makedirs(d, exist_ok=True)
+    info = solver.export_tablebase(os.path.join(d, "solution.gmtb"))
+    with open(os.path.join(d, "meta.json"), "w") as f:
+        json.dump({"game": spec.name, "params": spec.params,
+                   "root": result.root_line, "positions": info["positions"],
+                   "owned_by_rank": 0, "format": "gmtb", "word_bytes": info["word_bytes"],
+                   "value_codes": {"WIN": 0, "LOSS": 1, "TIE": 2, "DRAW": 3}},
+                  f, indent=1)
 
 
 def check_analysis_args(args, world, descriptor=True):
@@ -312,6 +349,7 @@ def main(argv=None):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     check_analysis_args(args, world)
+    check_tablebase_args(args, world)
     if args.debug:  # src/debug.py:10-18: logging to logs/proc<rank>
         os.makedirs("logs", exist_ok=True)
         logging.basicConfig(filename="logs/proc%d" % rank, level=logging.DEBUG)
@@ -332,10 +370,12 @@ def main(argv=None):
         if args.layout not in ("auto", "graph"):
             raise
         check_analysis_args(args, world, descriptor=False)
+        check_tablebase_args(args, world, descriptor=False)
         logging.debug("%s: solving through the host-enumerated graph", e)
         return solve_generic(args, game, rank, world, local)
     if args.layout == "graph":
         return solve_generic(args, game, rank, world, local)
+    check_tablebase_args(args, world, spec)
     if args.symmetries:
         if not hasattr(game, "symmetry_functions"):
             raise SystemExit("%s defines no symmetry_functions()" % args.game_file)
@@ -428,7 +468,9 @@ def main(argv=None):
             print(json.dumps(row), flush=True)
         if census:
             print(census[0], flush=True)
-    if args.statsdir:
+    if args.statsdir and args.tablebase:
+        write_tablebase_stats(args.statsdir, spec, solver, result)
+    elif args.statsdir:
         write_stats(args.statsdir, rank, spec, solver, result, world)
     rc = 0
     if args.line:

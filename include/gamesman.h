@@ -354,6 +354,48 @@ int gm_solver_census(gm_solver *s, uint32_t how,
                      uint64_t *by_rem_dev, uint32_t rem_bins,
                      uint64_t *by_level_dev, uint32_t levels,
                      uint64_t extremes[12]);
+/* ---- the indexed tablebase (solution.gmtb) ----------
+ * A position of an indexed game has a tablebase index computed from its key
+ * alone; a tablebase is a reach bitmap over the index space plus one compact
+ * word per reached index, in index order -- no keys.  Replaces, for those
+ * games, walking the resolved / remote shelves to save a solution
+ * (src/cache_dict.py:38-60).
+ *   four_to_one, sum_four_to_one: index = key (the mixed-radix rank); the
+ *     space is the product of (heap + 1), rounded up to GM_TB_BLOCK
+ *   toot_and_otto_bitstring: the RANKED slot (level-major: height vectors in
+ *     code order, blocks of 8 * 2^L slots, levels padded to GM_TB_BLOCK) -- a
+ *     function of the board size alone, whatever layout solved the table
+ * Host only, no GPU needed. */
+#define GM_NO_INDEX (~0ull)
+#define GM_TB_BLOCK 512u
+/* size of the game's index space (a multiple of GM_TB_BLOCK after padding).
+ * GM_EINVAL for games without an index function
+ * (tic_tac_toe_np, mttt, othello_bit_new). */
+int gm_tb_info(int game, uint64_t *index_space);
+/* index[i] = tablebase index of keys[i]; GM_NO_INDEX for a key that is no
+ * position of the game */
+int gm_tb_index(int game, const uint64_t *keys, size_t n, uint64_t *index);
+/* Indexes [first, first + count) of a finished solve as tablebase sections,
+ * written on the device: bit i of bits_dev (count / 64 u64) = index first + i
+ * is reached, block_counts_dev (count / GM_TB_BLOCK u32) = reached indexes
+ * per block, words_dev = the reached indexes' canonical words (value |
+ * remoteness << 2, as gm_solver_query) truncated to word_bytes (1, 2 or 4),
+ * in index order; words_dev 16-byte aligned.  first and count are multiples
+ * of GM_TB_BLOCK inside the padded index space.  *n_words = words written.
+ * GM_EFULL when words_cap is short (*n_words = the count needed; bits and
+ * block counts are complete); GM_EINVAL when a word does not fit word_bytes
+ * (gm_last_error names the remoteness), for a shard, for a solver without a
+ * finished full solve and for games without an index.  Synchronous on the
+ * solver's stream; reads the table only.  Exporting a range in pieces
+ * concatenates to the export of the whole range.  PLANES and RANKED tables
+ * are read in storage order by kernels of their own; how = GM_EXPORT_GENERIC
+ * takes them, as every other layout, through index -> key -> the query path
+ * (A/B runs, tests). */
+#define GM_EXPORT_GENERIC 1u
+int gm_solver_export(gm_solver *s, uint32_t how, uint64_t first, uint64_t count,
+                     uint32_t word_bytes, uint64_t *bits_dev,
+                     uint32_t *block_counts_dev, void *words_dev,
+                     uint64_t words_cap, uint64_t *n_words);
 /* change GM_F_* flags of an existing solver (e.g. kernel timing) */
 int gm_solver_set_flags(gm_solver *s, uint32_t flags);
 /* Level-granular stop / resume (checkpoints; SURVEY.md §8f rank 2 -- the
