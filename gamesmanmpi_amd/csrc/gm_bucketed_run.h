@@ -52,6 +52,14 @@ static u64 bk_shard_edges_bound(const Desc* d, u64 P) {
 // (+5% and a run per partition: the count-free expand provisions each of the
 // 256 coarse partitions a 1/256 share of it, k_bk_expand<OVER>)
 static u64 bk_emax_bound(u64 E) { return std::min<u64>(E, std::max<u64>(E / 4, 1u << 20)) / 20 * 21 + (u64)kBkC * 4096; }
+// bytes of the table buffer ahead of the staging, as bk_setup carves them:
+// the words, then the in-edges' parents (u32) and child indices (u16) -- a
+// second set on md5 shards -- each array padded so that the next one, and at
+// last the 8-byte staging keys, start aligned
+static u64 bk_fixed_bytes(u64 Pcap, u64 Ecap, int world) {
+  const u64 edges = 4 * Ecap + ((2 * Ecap + 7) & ~7ull);
+  return ((4 * Pcap + 7) & ~7ull) + (world > 1 ? 2 : 1) * edges;
+}
 struct BkScratch {
   size_t lv, pbase, bh, ph, boff, tot, cbase, ah, cur, ucnt, total, gc, meta, end;
 };
@@ -132,8 +140,10 @@ static void bk_setup(gm_solver* s, const gm_buffers* buf) {
   s->Ecap = buf->table_slots;
   // a shard of a world > 1 job also holds the md5 exchange buffers (24 B per staged record)
   // (world > 1 also: the local-dedup form's in-edges, another 6 B per edge)
-  s->Emax = std::min<u64>((buf->table_bytes - 4 * s->Pcap - (world > 1 ? 12 : 6) * s->Ecap) / (world > 1 ? 48 : 24),
-                          0xFFFFFFF0ull);
+  // (the padded sizes: with 4 Pcap + 6 Ecap the last staging array ended up
+  // to 10 bytes past table_bytes when Pcap was odd or Ecap no multiple of 4)
+  const u64 fixed = bk_fixed_bytes(s->Pcap, s->Ecap, world);
+  s->Emax = std::min<u64>((buf->table_bytes > fixed ? buf->table_bytes - fixed : 0) / (world > 1 ? 48 : 24), 0xFFFFFFF0ull);
   s->bkK = (u64*)buf->levels;
   s->bkW = (uint32_t*)t;
   t += (4 * s->Pcap + 7) & ~7ull;

@@ -312,6 +312,16 @@ static int run_bucketed_shards(std::vector<gm_solver*> ss, gm_result* out) {
   // every rank returns together.
   int prc = 0;
   std::string perr;
+  // Forward launches, summed over this process's shards (gm_result.
+  // n_expand_launches, as the one-GPU loop's nfwd).  Per (shard, level) whose
+  // shard holds parents: the count-free expand + its scan = 2; a redo of an
+  // overflowed level adds the count, two column scans and a scan = 4, and the
+  // exact expand = 1 (GM_F_BK_EXACT: those 5 alone); the local-dedup form
+  // then adds fine, dedup, scan and the owner binning = 4.  Per (shard, level)
+  // that receives records: hist, colscan, scan, part, fine, dedup, scan = 7,
+  // and the compact = 1.  So a solve with R redone (shard, level) pairs makes
+  // exactly 5 R more forward launches than the same solve with none.
+  u64 nfwd = 0;
   u64 host_err = 0;  // error bits found on the host (sent with the final totals)
   auto defer = [&](int code) {
     if (!prc) {
@@ -334,13 +344,16 @@ static int run_bucketed_shards(std::vector<gm_solver*> ss, gm_result* out) {
   // pass (the local in-edges' parents, REpl), the LDS dedup (REcl) and the
   // unique local children binned by owner (k_bks_ownbin, one MD5 each) into
   // the send regions; then the size matrix and the all-to-all as the
-  // occurrence form.  Two host syncs for all shards, plus the size matrix.
+  // occurrence form.  Two host syncs for all shards, plus the size matrix
+  // (a third when a shard's coarse partition overflowed its share and that
+  // shard redoes the level counted; an owner's region of unique children
+  // past Emax / W still fails the level with GM_EFULL).
   auto forward_local = [&](int L, std::vector<u64>& meta_at) -> int {
     struct Q {
       std::vector<uint32_t> g;
       uint32_t herr = 0, cap = 0;
       u64 NR = 0, nblk = 0, chunk = 0;
-      bool active = false;
+      bool active = false, redo = false;
     };
     std::vector<Q> q(ss.size());
     for (size_t gi = 0; gi < ss.size(); gi++) {
@@ -399,11 +412,36 @@ static int run_bucketed_shards(std::vector<gm_solver*> ss, gm_result* out) {
                            s->S1f, z.cap, s->bkgc, P.pshift, P.fb, s->bkgc + kBkC, rfo, s->bkgc + 2 * kBkC, s->st, ck);
       });
       hipLaunchKernelGGL(k_bk_scan, dim3(1), dim3(1024), 0, s->stream, rfo, (uint32_t)z.NR + 1, rfo, s->bktotal + 1);
+      nfwd += 2;
       HIPCHK(hipGetLastError());
       HIPCHK(hipMemcpyAsync(z.g.data(), s->bkgc, z.g.size() * 4, hipMemcpyDeviceToHost, s->stream));
       HIPCHK(hipMemcpyAsync(&z.herr, &s->st->err, 4, hipMemcpyDeviceToHost, s->stream));
     }
     HIPCHK(sync_all());
+    // a coarse partition past its provisioned share: that shard redoes the
+    // level counted, as the one-GPU loop does (k_bk_count, then the exact
+    // expand below); the others keep their count-free staging
+    bool any_redo = false;
+    for (size_t gi = 0; gi < ss.size(); gi++) {
+      gm_solver* s = ss[gi];
+      Q& z = q[gi];
+      if (!z.active || z.herr || !z.g[2 * kBkC]) continue;
+      z.redo = any_redo = true;
+      BkLevel& P = s->lvh[(size_t)L];
+      uint32_t* rfo = s->meta + P.rfo_off;
+      HIPCHK(hipMemsetAsync(rfo, 0, (z.NR + 1) * 4, s->stream));
+      BK_KIND_LAUNCH(k_bk_count, z.nblk, kBkStreamThreads, s, s->d, s->bkK + P.lb, P.n, z.chunk, P.pshift, P.fb, s->bh,
+                     s->ph, rfo, s->st);
+      hipLaunchKernelGGL(k_bk_colscan, dim3(kBkC), dim3(256), 0, s->stream, s->bh, (uint32_t)z.nblk, s->boff, s->tot);
+      hipLaunchKernelGGL(k_bk_colscan, dim3(kBkC), dim3(256), 0, s->stream, s->ph, (uint32_t)z.nblk, s->ph, s->tot + kBkC);
+      hipLaunchKernelGGL(k_bk_scan, dim3(1), dim3(1024), 0, s->stream, rfo, (uint32_t)z.NR + 1, rfo, s->bktotal + 1);
+      nfwd += 4;
+      HIPCHK(hipGetLastError());
+      z.g[2 * kBkC] = 0;
+      HIPCHK(hipMemcpyAsync(z.g.data(), s->tot, 2 * kBkC * 4, hipMemcpyDeviceToHost, s->stream));
+      HIPCHK(hipMemcpyAsync(&z.herr, &s->st->err, 4, hipMemcpyDeviceToHost, s->stream));
+    }
+    if (any_redo) HIPCHK(sync_all());
     std::vector<std::vector<uint32_t>> oc(ss.size(), std::vector<uint32_t>((size_t)W + 1, 0));
     std::vector<u64> nu(ss.size(), 0);
     std::vector<uint32_t> derr(ss.size(), 0);
@@ -415,11 +453,6 @@ static int run_bucketed_shards(std::vector<gm_solver*> ss, gm_result* out) {
       gm_solver::BksLocal& B = s->bksl[(size_t)L];
       if (z.herr) {
         defer(fail(GM_ECORRUPT, "shard %d level %d:%s", s->rank, L, err_text(z.herr).c_str()));
-        z.active = false;
-        continue;
-      }
-      if (z.g[2 * kBkC]) {  // a coarse partition past its provisioned share
-        defer(fail(GM_EFULL, "shard %d level %d: a partition of the local children exceeds its share", s->rank, L));
         z.active = false;
         continue;
       }
@@ -468,9 +501,20 @@ static int run_bucketed_shards(std::vector<gm_solver*> ss, gm_result* out) {
       uint32_t ck_sh = 14;
       while (ck_sh > 6 && (s->Emax / kBkC) < (1ull << ck_sh)) ck_sh--;
       const BkChunked ck{(char*)s->S1k, ck_sh};
+      if (z.redo) {  // E <= Emax was checked above, before this writes the staging
+        const uint32_t ppr = bk_ppr((double)E / (double)P.n);
+        bk_dispatch(s->d, [&](auto kind_) {
+          constexpr int K_ = decltype(kind_)::value;
+          hipLaunchKernelGGL((k_bk_expand<K_, false>), dim3(z.nblk), dim3(kBkExpandThreads), 0, s->stream, s->d,
+                             s->bkK + P.lb, P.n, z.chunk, (const uint32_t*)s->boff, (const uint32_t*)s->cbase, ppr, s->S1k,
+                             s->S1p, s->S1f, 0u, (uint32_t*)nullptr, 0u, 0u, (uint32_t*)nullptr, (uint32_t*)nullptr,
+                             (uint32_t*)nullptr, s->st, BkChunked{nullptr, 0});
+        });
+        nfwd++;
+      }
       hipLaunchKernelGGL(k_bk_fine, dim3(kBkC), dim3(kBkFineThreads), 0, s->stream, (const u64*)s->S1k, (const uint32_t*)s->S1p,
                          (const uint8_t*)s->S1f, (const uint32_t*)s->cbase, 8u - f, F, s->S2k, s->REpl + B.rb, fo,
-                         P.pshift, s->bkah + (size_t)L * kBkC * kBkC, z.cap, ck);
+                         P.pshift, s->bkah + (size_t)L * kBkC * kBkC, z.redo ? 0u : z.cap, ck);
       const int gd = (int)std::min<uint32_t>(NB, 512);
       hipLaunchKernelGGL(k_bk_dedup, dim3(gd), dim3(kBkDedupThreads), 0, s->stream, s->S2k, (const uint32_t*)fo, NB, s->S1k,
                          s->ucnt, s->REcl + B.rb, s->st);
@@ -483,6 +527,7 @@ static int run_bucketed_shards(std::vector<gm_solver*> ss, gm_result* out) {
                            (const uint32_t*)fo, (const uint32_t*)cst, NB, F, (uint32_t)W, (uint32_t)s->rank << 29, capd,
                            s->bkgc, s->XSk, s->XSr, s->bkgc + 2 * kBkC);
       });
+      nfwd += 4;
       HIPCHK(hipGetLastError());
       HIPCHK(hipMemcpyAsync(oc[gi].data(), s->bkgc, (size_t)W * 4, hipMemcpyDeviceToHost, s->stream));
       HIPCHK(hipMemcpyAsync(&oc[gi][(size_t)W], s->bkgc + 2 * kBkC, 4, hipMemcpyDeviceToHost, s->stream));
@@ -632,6 +677,7 @@ static int run_bucketed_shards(std::vector<gm_solver*> ss, gm_result* out) {
                            s->bkgc + 2 * kBkC, s->st, BkChunked{nullptr, 0}, (uint32_t)W, (uint32_t)s->rank << 29);
       });
       hipLaunchKernelGGL(k_bk_scan, dim3(1), dim3(1024), 0, s->stream, rfo, q.NR + 1, rfo, s->bktotal + 1);
+      nfwd += 2;
       HIPCHK(hipGetLastError());
       HIPCHK(hipMemcpyAsync(q.htot.data(), s->bkgc, q.htot.size() * 4, hipMemcpyDeviceToHost, s->stream));
       HIPCHK(hipMemcpyAsync(&q.herr, &s->st->err, 4, hipMemcpyDeviceToHost, s->stream));
@@ -659,6 +705,7 @@ static int run_bucketed_shards(std::vector<gm_solver*> ss, gm_result* out) {
       hipLaunchKernelGGL(k_bk_colscan, dim3(kBkC), dim3(256), 0, s->stream, s->bh, (uint32_t)q.nblk, s->boff, s->tot);
       hipLaunchKernelGGL(k_bk_colscan, dim3(kBkC), dim3(256), 0, s->stream, s->ph, (uint32_t)q.nblk, s->ph, s->tot + kBkC);
       hipLaunchKernelGGL(k_bk_scan, dim3(1), dim3(1024), 0, s->stream, rfo, q.NR + 1, rfo, s->bktotal + 1);
+      nfwd += 4;
       HIPCHK(hipGetLastError());
       HIPCHK(hipMemcpyAsync(q.htot.data(), s->tot, 2 * kBkC * 4, hipMemcpyDeviceToHost, s->stream));
       HIPCHK(hipMemcpyAsync(&q.herr, &s->st->err, 4, hipMemcpyDeviceToHost, s->stream));
@@ -748,6 +795,7 @@ static int run_bucketed_shards(std::vector<gm_solver*> ss, gm_result* out) {
                              (uint32_t*)nullptr, (uint32_t*)nullptr, s->st, BkChunked{nullptr, 0}, (uint32_t)W,
                              (uint32_t)r << 29);
         });
+        nfwd++;
         HIPCHK(hipGetLastError());
       }
       ak[g] = BksA2A{(char*)s->XSk, (char*)s->XRk, sc, std::vector<u64>(so.begin(), so.end() - 1), rcv,
@@ -800,6 +848,7 @@ static int run_bucketed_shards(std::vector<gm_solver*> ss, gm_result* out) {
       hipLaunchKernelGGL(k_bk_dedup, dim3(gd), dim3(kBkDedupThreads), 0, s->stream, s->S2k, (const uint32_t*)fo, NB, s->S1k,
                          s->ucnt, s->REc + X.rb, s->st);
       hipLaunchKernelGGL(k_bk_scan, dim3(1), dim3(1024), 0, s->stream, s->ucnt, NB, cst, s->bktotal);
+      nfwd += 7;
       HIPCHK(hipGetLastError());
       (void)P;
     }
@@ -831,6 +880,7 @@ static int run_bucketed_shards(std::vector<gm_solver*> ss, gm_result* out) {
       const uint32_t* cst = s->meta + X.cst_off;
       hipLaunchKernelGGL(k_bk_compact, dim3(std::min<uint32_t>(NB, 4096)), dim3(256), 0, s->stream, (const u64*)s->S1k,
                          (const uint32_t*)(cst + NB + 1), cst, NB, s->bkK + X.lb);
+      nfwd++;
       HIPCHK(hipGetLastError());
     }
     if (L + 2 < T) {  // the largest shard of level L + 1 (the next level's form)
@@ -997,6 +1047,7 @@ static int run_bucketed_shards(std::vector<gm_solver*> ss, gm_result* out) {
   out->ms_forward = fms;
   out->ms_backward = bms;
   out->ms_total = std::chrono::duration<double, std::milli>(t1 - t0).count();
+  out->n_expand_launches = nfwd;
   out->positions = tot[0];
   out->edges = tot[1];
   out->primitives = tot[2];

@@ -1693,7 +1693,7 @@ int gm_plan(int game, uint64_t positions, uint32_t flags, uint64_t max_table_byt
     // partition buffers of the widest level's in-edges (table buffer)
     const u64 P = positions + 64, E = bk_edges_bound(d, positions), Em = bk_emax_bound(E);
     if (Em >= 0xFFFFFFF0ull) return fail(GM_EINVAL, "a level of more than 2^32 edges: not supported");
-    const u64 bytes = 4 * P + 6 * E + 24 * Em;  // words, in-edges (u32 parent + u16 child), staging
+    const u64 bytes = bk_fixed_bytes(P, E, 1) + 24 * Em;  // words, in-edges (u32 parent + u16 child), staging
     // over the caller's byte budget: the keyed hash table instead (as a
     // dense table over budget falls back above)
     if (max_table_bytes == 0 || bytes <= max_table_bytes) {
@@ -1733,7 +1733,7 @@ int gm_plan_keyed_shard(int game, int rank, int world, uint64_t positions, uint3
   }
   const u64 P = positions + 64, E = bk_shard_edges_bound(d, positions), Em = bk_emax_bound(E);
   if (Em >= 0xFFFFFFF0ull) return fail(GM_EINVAL, "a level of more than 2^32 edges: not supported");
-  const u64 bytes = 4 * P + 12 * E + 48 * Em + 64;  // the one-GPU layout + local in-edges + the exchange buffers
+  const u64 bytes = bk_fixed_bytes(P, E, 2) + 48 * Em + 64;  // the one-GPU layout + local in-edges + the exchange buffers
   if (max_table_bytes && bytes > max_table_bytes)
     return fail(GM_EFULL, "bucketed shard needs %llu bytes", (unsigned long long)bytes);
   out->mode = GM_MODE_BUCKETED;
@@ -1776,7 +1776,7 @@ int gm_solver_create_shard(int game, int rank, int world, const gm_buffers* buf,
     if (!bk_ok(d)) return fail(GM_EINVAL, "bucketed levels need every move to advance one level");
     if (!buf->levels || buf->level_capacity < 2) return fail(GM_EINVAL, "null level store");
     if (buf->scratch_bytes < bk_scratch(d->max_levels).end) return fail(GM_EINVAL, "scratch too small (use gm_plan)");
-    const u64 fixed = 4 * buf->level_capacity + 6 * buf->table_slots;
+    const u64 fixed = bk_fixed_bytes(buf->level_capacity, buf->table_slots, world);
     if (buf->table_bytes < fixed + (world > 1 ? 48 : 24) * 1024ull)
       return fail(GM_EINVAL, "bucketed table too small (use gm_plan / gm_plan_keyed_shard)");
   } else if (buf->mode == GM_MODE_HASHED) {

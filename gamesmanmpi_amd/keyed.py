@@ -390,15 +390,19 @@ def _pick(spec, world, layout):
     return "hashed"
 
 
-def group_keyed_solve(spec, world, device=None, layout="auto", flags=0, streams="one"):
+def group_keyed_solve(spec, world, device=None, layout="auto", flags=0, streams="one",
+                      staging_records=0, prepare=None):
     """Every md5 shard of a `world`-rank job in this process, on one GPU.
     layout "auto": md5-sharded BUCKETED levels where they apply (the
     library's all-to-all level loop, gm_bucketed_shard.h), else HASHED
     shards driven by keyed_solve.  streams "one": every shard on one stream;
     "own" (bucketed): each shard on a stream of its own, the all-to-alls as
     device copies between them -- the one-GPU rehearsal of the RCCL
-    stream order.  Returns (SolveResult, shards): Solvers (bucketed) or
-    GpuShards (hashed), both with dump()."""
+    stream order.  staging_records (bucketed): every shard's staging capacity
+    (Solver); prepare (bucketed): called with the list of shards once they
+    exist and before they solve, so a caller can mark their buffers and
+    still holds them when the solve raises.  Returns (SolveResult, shards):
+    Solvers (bucketed) or GpuShards (hashed), both with dump()."""
     import torch
     from .dist import _group_streams
     spec = spec if isinstance(spec, GameSpec) else GameSpec(*spec)
@@ -409,8 +413,11 @@ def group_keyed_solve(spec, world, device=None, layout="auto", flags=0, streams=
     if pick in ("bucketed", "ranked"):
         per = _shard_bound(spec, world, 0)
         shards = [Solver(spec, positions=per, device=dev, layout=pick,
-                         rank=g, world=world, stream=ss[g], flags=flags)
+                         rank=g, world=world, stream=ss[g], flags=flags,
+                         staging_records=staging_records)
                   for g in range(world)]
+        if prepare is not None:
+            prepare(shards)
         arr = (ctypes.c_void_p * world)(*[s.handle.value for s in shards])
         r = _lib.gm_result()
         torch.cuda.synchronize(dev)
@@ -419,6 +426,8 @@ def group_keyed_solve(spec, world, device=None, layout="auto", flags=0, streams=
         res = shards[0]._result(r)
         res.extra.update({"partition": "md5", "world": world})
         return res, shards
+    if staging_records:
+        raise ValueError("staging_records applies to bucketed layouts only")
     shards = [GpuShard(spec, g, world, device=dev, stream=stream)
               for g in range(world)]
     return keyed_solve(shards, GroupExchange()), shards

@@ -48,7 +48,7 @@ class Solver:
 
     def __init__(self, spec, positions=0, device=None, kernel_timing=False,
                  layout="auto", max_table_bytes=0, rank=0, world=1,
-                 stream=None, flags=0):
+                 stream=None, flags=0, staging_records=0):
         """layout: "auto" (planes, else the level-major dense table, when
         the descriptor supports it and the table fits max_table_bytes; the
         ranked table for toot-and-otto; else bucketed levels when every move
@@ -63,7 +63,12 @@ class Solver:
         GPU solve (gamesmanmpi_amd.dist), or with layout="bucketed" /
         "hashed" one md5 shard of a keyed solve (gamesmanmpi_amd.keyed;
         `positions` is then this shard's bound); stream: a torch stream to
-        run on."""
+        run on.  staging_records=N (bucketed layouts, one GPU or md5 shard):
+        the buffers keep the plan's sizes, but the library is told a table
+        that ends where N staging records per level end (claimed_table_bytes),
+        so the solve runs with that staging capacity and never regrows; the
+        bytes past the claimed end are the caller's (capacity tests keep a
+        canary there)."""
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("gamesmanmpi_amd needs a ROCm GPU (gfx950); "
@@ -81,6 +86,8 @@ class Solver:
         if flags & ~_lib.KERNEL_FLAGS:
             raise ValueError("flags: kernel-family flags only (%#x)" % _lib.KERNEL_FLAGS)
         self.flags = int(flags)
+        self.staging_records = int(staging_records)
+        self.claimed_table_bytes = None
         self.positions_hint = int(positions or self.spec.positions_bound)
         # the layout planned: `layout`, except that "auto" falls back to the
         # hashed table when a bucketed plan hits a layout limit (solve())
@@ -145,6 +152,22 @@ class Solver:
         b.flags = flags | (_lib.GM_F_KERNEL_TIMING if self.kernel_timing else 0)
         b.mode = plan.mode
         b.table_bytes = plan.table_bytes
+        if self.staging_records:
+            if plan.mode != _lib.GM_MODE_BUCKETED:
+                raise ValueError("staging_records applies to bucketed layouts only")
+            # words, in-edges (a second set on md5 shards) and 24 B (48 B with
+            # the exchange buffers) per staging record: 4 level_capacity +
+            # K table_slots + R N with K, R = 6, 24 (12, 48), each array
+            # padded to 8 bytes as bk_setup carves them, so its Emax == N
+            sets, r = (1, 24) if self.world == 1 else (2, 48)
+            slots = int(plan.table_slots)
+            b.table_bytes = ((4 * int(plan.level_capacity) + 7 & ~7)
+                             + sets * (4 * slots + (2 * slots + 7 & ~7))
+                             + r * self.staging_records)
+            if b.table_bytes > plan.table_bytes:
+                raise ValueError("staging_records=%d exceeds the plan's table"
+                                 % self.staging_records)
+        self.claimed_table_bytes = int(b.table_bytes)
         self._bufs = b
         self._cflags = flags  # the flags the solver was created with (layout bits included)
         self.plan = plan
@@ -187,8 +210,8 @@ class Solver:
         """Full solve from the root; grows the buffers on GM_EFULL."""
         L = _lib.load()
         r = _lib.gm_result()
-        if self.world > 1:
-            max_retries = 0  # shard tables are sized exactly
+        if self.world > 1 or getattr(self, "staging_records", 0):
+            max_retries = 0  # shard tables are sized exactly; a chosen capacity stays
         attempt = 0
         while True:
             try:

@@ -720,6 +720,37 @@ int or_dump(void *hs, uint8_t *canon, int stride, uint8_t *clen, uint8_t *value,
   return 0;
 }
 
+/* Every edge of the solved graph, table order as or_dump: row e holds the
+ * parent's and the child's canonical bytes (rows of `stride` bytes, zero
+ * padded) and their lengths; a primitive position has no row.  or_edges()
+ * rows in all. */
+int or_edge_list(void *hs, uint8_t *pcanon, uint8_t *plen, uint8_t *ccanon, uint8_t *clen, int stride) {
+  solve_t *S = hs;
+  const game *g = G(S->game);
+  uint64_t e = 0;
+  uint8_t tmp[32], ptmp[32];
+  blob ch[OR_MAXCHILD];
+  for (uint64_t i = 0; i < S->cap; i++) {
+    if (!S->tab[i].used) continue;
+    if (prim_of(g, &S->tab[i].key) != UNDECIDED) continue;
+    int pn = to_canon(g, &S->tab[i].key, ptmp);
+    if (pn > stride) return -1;
+    int nch = children_of(g, &S->tab[i].key, ch);
+    for (int c = 0; c < nch; c++, e++) {
+      if (e >= S->edges) return -2;
+      int n = to_canon(g, &ch[c], tmp);
+      if (n > stride) return -1;
+      memset(pcanon + e * (uint64_t)stride, 0, (size_t)stride);
+      memcpy(pcanon + e * (uint64_t)stride, ptmp, (size_t)pn);
+      plen[e] = (uint8_t)pn;
+      memset(ccanon + e * (uint64_t)stride, 0, (size_t)stride);
+      memcpy(ccanon + e * (uint64_t)stride, tmp, (size_t)n);
+      clen[e] = (uint8_t)n;
+    }
+  }
+  return e == S->edges ? 0 : -2;
+}
+
 /* Look up one position's word (or 0xFFFFFFFF if unknown). */
 uint32_t or_lookup(void *hs, const uint8_t *canon, int len) {
   solve_t *S = hs;

@@ -48,6 +48,9 @@ def lib():
         L.or_dump.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                               ctypes.c_void_p, ctypes.c_void_p,
                               ctypes.c_void_p]
+        L.or_edge_list.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                   ctypes.c_void_p, ctypes.c_void_p,
+                                   ctypes.c_void_p, ctypes.c_int]
         L.or_lookup.argtypes = [ctypes.c_void_p, ctypes.c_char_p,
                                 ctypes.c_int]
         L.or_lookup.restype = ctypes.c_uint32
@@ -222,6 +225,22 @@ class Solution:
         order = sorted(range(n), key=lambda i: bytes(canon[i, :clen[i]]))
         order = np.array(order, dtype=np.int64)
         return canon[order], clen[order], val[order], rem[order]
+
+    def edge_list(self, stride=24):
+        """Every edge of the solved graph, one row per (parent, child) in
+        gen_moves order: (parent canon u8[e, stride], parent lengths u8[e],
+        child canon, child lengths), e == self.edges.  Per-level out-edge
+        counts and owner / partition histograms are group-bys over it."""
+        e = self.edges
+        pc = np.zeros((e, stride), np.uint8)
+        pl = np.zeros(e, np.uint8)
+        cc = np.zeros((e, stride), np.uint8)
+        cl = np.zeros(e, np.uint8)
+        rc = lib().or_edge_list(self.h, pc.ctypes.data, pl.ctypes.data,
+                                cc.ctypes.data, cl.ctypes.data, stride)
+        if rc:
+            raise RuntimeError("edge_list failed (%d)" % rc)
+        return pc, pl, cc, cl
 
     def lookup(self, canon):
         w = lib().or_lookup(self.h, canon, len(canon))
