@@ -58,6 +58,7 @@ GM_CENSUS_GENERIC = 1  # gm_solver_census `how`: enumerator + query path on ever
 GM_EXPORT_GENERIC = 1  # gm_solver_export `how`: index -> key -> query path on every layout
 GM_NO_INDEX = 0xFFFFFFFFFFFFFFFF  # gm_tb_index: the key is no position of the game
 GM_TB_BLOCK = 512  # tablebase indexes per block
+GM_TK_BUCKET_CAP = 1024  # gm_solver_export_keyed: positions of one bucket
 
 
 class GmError(RuntimeError):
@@ -131,6 +132,7 @@ EXPORTS = (
     "gm_ks_finalize", "gm_ks_counts", "gm_ks_children", "gm_ks_reduce",
     "gm_ks_end", "gm_graph_solve",
     "gm_tb_info", "gm_tb_index", "gm_solver_export",
+    "gm_mix64", "gm_solver_export_keyed",
     "gm_last_error", "gm_version",
 )
 
@@ -189,7 +191,10 @@ def load():
         "gm_tb_index": [c.c_int, c.c_void_p, c.c_size_t, c.c_void_p],
         "gm_solver_export": [c.c_void_p, c.c_uint32, c.c_uint64, c.c_uint64, c.c_uint32, c.c_void_p,
                              c.c_void_p, c.c_void_p, c.c_uint64, P(c.c_uint64)],
-        "gm_solve": [c.c_int, c.c_uint64, c.c_int, P(gm_buffers),
+        "gm_mix64": [c.c_void_p, c.c_size_t, c.c_void_p],
+        "gm_solver_export_keyed": [c.c_void_p, c.c_uint32, c.c_uint32, c.c_uint32, c.c_void_p, c.c_void_p,
+                                   c.c_void_p, c.c_void_p, c.c_uint64, c.c_void_p],
+        "gm_solve":[c.c_int, c.c_uint64, c.c_int, P(gm_buffers),
                      P(gm_result)],
         "gm_plan_multi": [c.c_int, c.c_int, c.c_uint64, c.c_uint32, c.c_uint64, P(gm_plan_t)],
         "gm_query": [c.c_int, c.c_void_p, c.c_size_t, c.c_void_p],

@@ -606,7 +606,7 @@ static void build_colperm(const Desc* d, const ColGeom& c, std::vector<uint32_t>
   for (u64 k = 0; k < c.C; k++) perm[at[gs[k]]++] = (uint32_t)k;  // stable: address order within a sum
 }
 
-__device__ __forceinline__ u64 mix64(u64 x) {  // splitmix64 finaliser
+GM_HD u64 mix64(u64 x) {  // splitmix64 finaliser (host: gm_mix64, the keyed tablebase's reader)
   x ^= x >> 31;
   x *= 0x7fb5d329728ea185ull;
   x ^= x >> 27;
@@ -2090,6 +2090,26 @@ int gm_solver_export(gm_solver* s, uint32_t how, uint64_t first, uint64_t count,
                 (unsigned long long)first, (unsigned long long)count, GM_TB_BLOCK, (unsigned long long)space);
   if (!count) return 0;
   return export_run(s, how, first, count, word_bytes, (u64*)bits_dev, block_counts_dev, words_dev, words_cap, n_words);
+}
+
+#include "gm_export_keyed.h"
+
+int gm_mix64(const uint64_t* keys, size_t n, uint64_t* out) {
+  if (n && (!keys || !out)) return fail(GM_EINVAL, "bad argument");
+  for (size_t i = 0; i < n; i++) out[i] = mix64(keys[i]);
+  return 0;
+}
+
+int gm_solver_export_keyed(gm_solver* s, uint32_t how, uint32_t bucket_bits, uint32_t word_bytes, void* stage_dev,
+                           uint64_t* dir_dev, void* keys_dev, void* words_dev, uint64_t cap, uint64_t out[4]) {
+  if (!s || !out || !dir_dev || (how & ~GM_EXPORT_GENERIC) || bucket_bits > 32 ||
+      (word_bytes != 1 && word_bytes != 2 && word_bytes != 4) || (cap && (!stage_dev || !keys_dev || !words_dev)) ||
+      (((uintptr_t)keys_dev | (uintptr_t)words_dev) & 15u) || (((uintptr_t)stage_dev | (uintptr_t)dir_dev) & 7u))
+    return fail(GM_EINVAL, "bad argument");
+  out[0] = out[1] = out[2] = out[3] = 0;
+  const int rc = moves_ready(s, "gm_solver_export_keyed");
+  if (rc) return rc;
+  return export_keyed_run(s, how, bucket_bits, word_bytes, stage_dev, (u64*)dir_dev, keys_dev, words_dev, cap, out);
 }
 
 int gm_solver_query(gm_solver* s, const uint64_t* keys_dev, uint64_t n, uint32_t* words_dev) {

@@ -40,6 +40,14 @@ on it unchanged, except that --census prints the remoteness table only.
     python -m gamesmanmpi_amd.db DIR --game GAME_FILE --to-tablebase
 
 converts a directory's solution.npz files to that file (write_tablebase).
+
+The other descriptor games (tic_tac_toe_np, mttt, othello_bit_new) have no
+index function; their counterpart is the keyed tablebase
+`<DIR>/stats/0/solution.gmtk` (Solver.export_keyed_tablebase; the format, its
+numpy writer write_keyed_tablebase and its reader KeyedTablebase are below):
+truncated keys grouped by hash bucket and sorted inside a bucket, one compact
+word per key.  `-sd DIR --tablebase` and `--to-tablebase` write it for those
+games, and SolutionDB opens it the same way.
 """
 import argparse
 import ast
@@ -223,9 +231,209 @@ class Tablebase:
         return by_rem
 
 
+# ---------------------------------------------------------------------------
+# the keyed tablebase, solution.gmtk
+# ---------------------------------------------------------------------------
+# For games without an index function (tic_tac_toe_np, mttt, othello_bit_new;
+# any keyed table works).  bucket(key) = the top bucket_bits bits of
+# mix64(key), 0 when bucket_bits is 0.  The file holds, little-endian:
+#   header     64 bytes: magic "GMTBKEY1", u32 version, u32 word_bytes, u32
+#              key_bytes, u32 bucket_bits, then u64 positions, directory
+#              offset, keys offset, words offset, file bytes
+#   directory  2^bucket_bits + 1 u64: dir[h] = positions in buckets below h
+#   keys       positions * key_bytes: the low key_bytes bytes of each key,
+#              by bucket, then by key ascending (key_bytes holds the OR of all
+#              keys, at least 1)
+#   words      positions * word_bytes: value | remoteness << 2, same order
+# A lookup reads two directory entries and binary-searches one bucket (about
+# 256 keys at the default bucket_bits); nothing is loaded up front.
+TK_MAGIC = b"GMTBKEY1"
+TK_VERSION = 1
+TK_HEADER = 64
+TK_NAME = "solution.gmtk"
+TK_BUCKET = 256  # positions per bucket the default bucket_bits aims at
+
+
+def mix64(keys):
+    """gm_mix64 in numpy: the hash whose top bits choose a key's bucket."""
+    x = np.array(keys, dtype=np.uint64, copy=True, ndmin=1)
+    with np.errstate(over="ignore"):
+        x ^= x >> np.uint64(31)
+        x *= np.uint64(0x7fb5d329728ea185)
+        x ^= x >> np.uint64(27)
+        x *= np.uint64(0x81dadef4bc2dd44d)
+        x ^= x >> np.uint64(33)
+    return x
+
+
+def tk_bucket(keys, bucket_bits):
+    """Bucket of each key, as int64."""
+    if not bucket_bits:
+        return np.zeros(len(np.atleast_1d(keys)), np.int64)
+    return (mix64(keys) >> np.uint64(64 - bucket_bits)).astype(np.int64)
+
+
+def tk_default_bits(positions):
+    """The smallest bucket_bits for which positions / 2^bits <= TK_BUCKET."""
+    b = 0
+    while positions > TK_BUCKET << b:
+        b += 1
+    return b
+
+
+def tk_header(word_bytes, key_bytes, bucket_bits, positions):
+    """The 64 header bytes, the three section offsets and the file's bytes."""
+    if word_bytes not in _TB_DTYPES or not 1 <= key_bytes <= 8 or not 0 <= bucket_bits <= 32:
+        raise ValueError("word bytes %d / key bytes %d / bucket bits %d" % (word_bytes, key_bytes, bucket_bits))
+    dir_off = TK_HEADER
+    keys_off = dir_off + 8 * ((1 << bucket_bits) + 1)
+    words_off = keys_off + positions * key_bytes
+    total = words_off + positions * word_bytes
+    head = TK_MAGIC + np.array([TK_VERSION, word_bytes, key_bytes, bucket_bits], "<u4").tobytes() + np.array(
+        [positions, dir_off, keys_off, words_off, total], "<u8").tobytes()
+    assert len(head) == TK_HEADER
+    return head, dir_off, keys_off, words_off, total
+
+
+def tk_key_bytes(keys):
+    """Bytes that hold the OR of `keys` (at least 1)."""
+    top = int(np.bitwise_or.reduce(np.asarray(keys, np.uint64))) if len(keys) else 0
+    return max(1, (top.bit_length() + 7) // 8)
+
+
+def write_keyed_tablebase(path, keys, words, word_bytes, bucket_bits=None):
+    """Write solution.gmtk from (key, word) pairs on the host (pure numpy; the
+    device writer is Solver.export_keyed_tablebase, which this restates byte
+    for byte).  words: value | remoteness << 2.  Returns bucket_bits."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    if len(keys) != len(words):
+        raise ValueError("%d keys, %d words" % (len(keys), len(words)))
+    b = tk_default_bits(len(keys)) if bucket_bits is None else int(bucket_bits)
+    if word_bytes < 4 and len(words) and int(words.max()) >> (8 * word_bytes):
+        raise ValueError("remoteness %d does not fit words of %d byte(s)" % (int(words.max()) >> 2, word_bytes))
+    kb = tk_key_bytes(keys)
+    head, _, _, _, _ = tk_header(word_bytes, kb, b, len(keys))
+    h = tk_bucket(keys, b)
+    order = np.lexsort((keys, h))
+    keys, words, h = keys[order], words[order], h[order]
+    if len(keys) > 1 and (np.diff(keys) == 0).any():  # (equal keys share a bucket: neighbours after the sort)
+        raise ValueError("a key appears twice")
+    directory = np.zeros((1 << b) + 1, "<u8")
+    directory[1:] = np.cumsum(np.bincount(h, minlength=1 << b))
+    tmp = path + ".tmp"
+    with open(tmp, "wb") as f:
+        f.write(head)
+        f.write(directory.tobytes())
+        f.write(np.ascontiguousarray(keys.astype("<u8").view(np.uint8).reshape(-1, 8)[:, :kb]).tobytes())
+        f.write(words.astype(_TB_DTYPES[word_bytes]).tobytes())
+    os.replace(tmp, path)
+    return b
+
+
+class KeyedTablebase:
+    """solution.gmtk opened with np.memmap: the three sections are mapped,
+    nothing is read until a lookup touches it.  The header is checked against
+    the file's size before anything is mapped; a lookup checks the directory
+    entries it reads (check_directory() reads all of them)."""
+
+    def __init__(self, path, spec=None):
+        self.path, self.spec = path, spec
+        size = os.path.getsize(path)
+        with open(path, "rb") as f:
+            head = f.read(TK_HEADER)
+        if len(head) < TK_HEADER or head[:8] != TK_MAGIC:
+            raise ValueError("%s is no keyed tablebase (bad magic)" % path)
+        version, wb, kb, b = (int(x) for x in np.frombuffer(head, "<u4", 4, 8))
+        npos, dir_off, keys_off, words_off, total = (int(x) for x in np.frombuffer(head, "<u8", 5, 24))
+        if version != TK_VERSION:
+            raise ValueError("%s: keyed tablebase version %d, this reader knows %d" % (path, version, TK_VERSION))
+        try:
+            want = tk_header(wb, kb, b, npos)
+        except ValueError as e:
+            raise ValueError("%s: bad header (%s)" % (path, e))
+        if (dir_off, keys_off, words_off, total) != want[1:]:
+            raise ValueError("%s: section offsets do not match the header's sizes" % path)
+        if size != total:
+            raise ValueError("%s holds %d bytes, its header says %d (truncated?)" % (path, size, total))
+        self.positions, self.word_bytes, self.key_bytes, self.bucket_bits = npos, wb, kb, b
+        self.dir = np.memmap(path, "<u8", "r", dir_off, ((1 << b) + 1,))
+        self.keys = (np.memmap(path, np.uint8, "r", keys_off, (npos, kb)) if npos
+                     else np.zeros((0, kb), np.uint8))
+        self.words = (np.memmap(path, _TB_DTYPES[wb], "r", words_off, (npos,)) if npos
+                      else np.zeros(0, _TB_DTYPES[wb]))
+        if int(self.dir[0]) != 0 or int(self.dir[-1]) != npos:  # (the directory's two ends: every lookup's bounds)
+            raise ValueError("%s: the directory counts %d..%d positions, the header %d"
+                             % (path, int(self.dir[0]), int(self.dir[-1]), npos))
+
+    def __len__(self):
+        return self.positions
+
+    def check_directory(self, chunk=1 << 22):
+        """Read the whole directory: ValueError unless it never decreases."""
+        n = len(self.dir)
+        for a in range(0, n - 1, chunk):
+            d = np.asarray(self.dir[a:a + chunk + 1])
+            if len(d) > 1 and (d[1:] < d[:-1]).any():
+                raise ValueError("%s: the directory decreases" % self.path)
+
+    def _key_at(self, at):
+        """u64 keys stored at positions `at` (int64 array)."""
+        buf = np.zeros((len(at), 8), np.uint8)
+        buf[:, :self.key_bytes] = self.keys[at]
+        return buf.view("<u8")[:, 0]
+
+    def lookup_keys(self, keys):
+        """uint32 words (value | remoteness << 2) of packed u64 keys; NO_WORD
+        for a key the table does not hold.  One bucket range per query, then
+        ceil(log2(largest range + 1)) binary-search steps over all of them."""
+        q = np.ascontiguousarray(keys, dtype=np.uint64)
+        out = np.full(len(q), NO_WORD, np.uint32)
+        ok = np.ones(len(q), bool)
+        if self.key_bytes < 8:  # a bit above the stored bytes: absent, no search
+            ok = (q >> np.uint64(8 * self.key_bytes)) == 0
+        if not ok.any() or not self.positions:
+            return out
+        q = q[ok]
+        h = tk_bucket(q, self.bucket_bits)
+        lo = np.asarray(self.dir[h]).astype(np.int64)
+        end = np.asarray(self.dir[h + 1]).astype(np.int64)
+        if (end < lo).any() or (end > self.positions).any():
+            raise ValueError("%s: the directory decreases or passes the position count" % self.path)
+        hi = end.copy()
+        for _ in range(int((hi - lo).max()).bit_length()):  # lower bound of q in [lo, hi)
+            act = np.flatnonzero(lo < hi)
+            if not len(act):
+                break
+            mid = (lo[act] + hi[act]) >> 1
+            less = self._key_at(mid) < q[act]
+            lo[act] = np.where(less, mid + 1, lo[act])
+            hi[act] = np.where(less, hi[act], mid)
+        cand = np.flatnonzero(lo < end)
+        hit = cand[self._key_at(lo[cand]) == q[cand]]
+        res = np.full(len(q), NO_WORD, np.uint32)
+        res[hit] = np.asarray(self.words[lo[hit]]).astype(np.uint32)
+        out[ok] = res
+        return out
+
+    def lookup_key(self, key):
+        w = int(self.lookup_keys(np.array([key], np.uint64))[0])
+        return None if w == NO_WORD else (w & 3, w >> 2)
+
+    by_remoteness = Tablebase.by_remoteness
+
+
 class SolutionDB:
     def __init__(self, root):
         tb = os.path.join(root, "stats", "0", TB_NAME)
+        tk = os.path.join(root, "stats", "0", TK_NAME)
+        if os.path.exists(tk) and not os.path.exists(tb):
+            # a keyed tablebase (one-GPU solves of games without an index): mapped, not loaded
+            with open(os.path.join(os.path.dirname(tk), "meta.json")) as f:
+                self.meta = json.load(f)
+            self.by, self.ranks = "key", 1
+            self.tablebase = KeyedTablebase(tk)
+            return
         if os.path.exists(tb):
             # an indexed tablebase (one-GPU solves of indexed games): mapped, not loaded
             with open(os.path.join(os.path.dirname(tb), "meta.json")) as f:
@@ -395,28 +603,42 @@ def position_moves(db, mod, pos, spec=None):
 
 
 def convert_to_tablebase(root, spec):
-    """stats/<rank>/solution.npz of a keyed table of an indexed game ->
-    stats/0/solution.gmtb (+ "format": "gmtb" in its meta.json).  The npz
-    files stay; SolutionDB prefers the tablebase."""
+    """stats/<rank>/solution.npz of a keyed table -> stats/0/solution.gmtb
+    for an indexed game, stats/0/solution.gmtk for a game without an index
+    (+ "format": "gmtb" / "gmtk" in its meta.json).  The npz files stay;
+    SolutionDB prefers the tablebase."""
     db = SolutionDB(root)
     if db.tablebase is not None:
         raise ValueError("%r already holds a tablebase" % root)
     if db.by != "key":
         raise ValueError("graph tables (by position name) have no index")
-    idx = spec.tb_index(db.keys)
-    if (idx == np.uint64(NO_INDEX)).any():
-        raise ValueError("the table holds keys that are no position of %r" % (spec,))
+    from . import _lib
+    try:
+        space = spec.tb_index_space()
+    except _lib.GmError:
+        space = None  # no index function: the keyed tablebase
     words = db.value.astype(np.uint32) | (db.remoteness.astype(np.uint32) << 2)
     wb = tb_word_bytes(int(db.remoteness.max()) if len(db) else 0)
     d = os.path.join(root, "stats", "0")
     os.makedirs(d, exist_ok=True)
-    meta = dict(db.meta, game=spec.name, params=spec.params, positions=len(db), format="gmtb",
-                word_bytes=wb)
+    meta = dict(db.meta, positions=len(db), word_bytes=wb)
     meta.pop("owned_by_rank", None)
-    write_tablebase(os.path.join(d, TB_NAME), spec.tb_index_space(), idx, words, wb)
+    if space is None:
+        # (game and params stay the table's own: a symmetric solve's are its key map)
+        path = os.path.join(d, TK_NAME)
+        meta.setdefault("game", spec.name)
+        meta.setdefault("params", spec.params)
+        meta.update(format="gmtk",bucket_bits=write_keyed_tablebase(path, db.keys, words, wb))
+    else:
+        idx = spec.tb_index(db.keys)
+        if (idx == np.uint64(NO_INDEX)).any():
+            raise ValueError("the table holds keys that are no position of %r" % (spec,))
+        path = os.path.join(d, TB_NAME)
+        meta.update(game=spec.name, params=spec.params, format="gmtb")
+        write_tablebase(path, space, idx, words, wb)
     with open(os.path.join(d, "meta.json"), "w") as f:
         json.dump(meta, f, indent=1)
-    return os.path.join(d, TB_NAME)
+    return path
 
 
 def main(argv=None):
@@ -435,7 +657,8 @@ def main(argv=None):
     ap.add_argument("--to-tablebase", action="store_true",
                     help="convert the directory's solution.npz files to the indexed tablebase "
                          "stats/0/solution.gmtb (indexed games: four_to_one, sum_four_to_one, "
-                         "toot_and_otto_bitstring) and exit")
+                         "toot_and_otto_bitstring) or, for the other descriptor games, to the keyed "
+                         "tablebase stats/0/solution.gmtk, and exit")
     ap.add_argument("positions", nargs="*")
     args = ap.parse_intermixed_args(argv)
     from . import _lib

@@ -503,6 +503,80 @@ class Solver:
         os.replace(tmp, path)
         return {"path": path, "bytes": words_off + npos * wb, "positions": npos, "word_bytes": wb}
 
+    # -- the keyed tablebase (gm_solver_export_keyed; db.KeyedTablebase reads it) --
+    def _export_keyed(self, bucket_bits, word_bytes, generic, cap):
+        """One gm_solver_export_keyed call: (rc, out u64[4], dir, keys, words)."""
+        torch = self.torch
+        stage = torch.empty(max(2, cap * 3 // 2 + 1), dtype=torch.int64, device=self.device)  # cap * 12 bytes
+        d = torch.empty((1 << bucket_bits) + 1, dtype=torch.int64, device=self.device)
+        keys = torch.empty(max(16, cap * 8), dtype=torch.uint8, device=self.device)
+        words = torch.empty(max(16, cap * word_bytes), dtype=torch.uint8, device=self.device)
+        out = np.zeros(4, np.uint64)
+        with torch.cuda.device(self.device):
+            rc = _lib.load().gm_solver_export_keyed(
+                self._h, _lib.GM_EXPORT_GENERIC if generic else 0, bucket_bits, word_bytes,
+                stage.data_ptr(), d.data_ptr(), keys.data_ptr(), words.data_ptr(), cap, out.ctypes.data)
+        return rc, out, d, keys, words
+
+    def export_keyed(self, bucket_bits, word_bytes, generic=False, cap=None):
+        """Keyed tablebase sections as device tensors (gm_solver_export_keyed):
+        (dir int64[2^bucket_bits + 1], keys uint8[n * key_bytes], words
+        uint8[n * word_bytes]) -- the keys by bucket, then ascending, each cut
+        to key_bytes = keys.numel() // n bytes.  cap: room for that many
+        positions (default: the census' count); TableFull when it is short or
+        a bucket holds more than 1,024 positions."""
+        bucket_bits, word_bytes = int(bucket_bits), int(word_bytes)
+        if cap is None:
+            cap = sum(e["count"] for e in self.census(rem_bins=0, levels=False)["extremes"])
+        rc, out, d, keys, words = self._export_keyed(bucket_bits, word_bytes, generic, int(cap))
+        _lib.check(rc)
+        n, kb = int(out[0]), int(out[1])
+        return d, keys[:n * kb], words[:n * word_bytes]
+
+    def export_keyed_tablebase(self, path, bucket_bits=None, generic=False, chunk=1 << 26):
+        """Write the finished solve as the keyed tablebase `path`
+        (solution.gmtk, db.KeyedTablebase): a directory of hash buckets, the
+        truncated keys sorted inside each bucket and one compact word per key,
+        all produced on the device and streamed to the file through one pinned
+        host buffer of `chunk` bytes -- no host copy of the table.  The word
+        width comes from the census' largest remoteness; bucket_bits defaults
+        to about 256 positions per bucket and grows while a bucket holds more
+        than the device sort's 1,024.  Returns dict(path, bytes, positions,
+        word_bytes, key_bytes, bucket_bits)."""
+        import os
+        from . import db
+        torch = self.torch
+        ext = self.census(rem_bins=0, levels=False)["extremes"]
+        npos = sum(e["count"] for e in ext)
+        wb = db.tb_word_bytes(max(e["max_remoteness"] for e in ext))
+        b = db.tk_default_bits(npos) if bucket_bits is None else int(bucket_bits)
+        while True:
+            rc, out, d, keys, words = self._export_keyed(b, wb, generic, npos)
+            if rc == _lib.GM_EFULL and int(out[2]) > _lib.GM_TK_BUCKET_CAP and b < 32:
+                b += 1  # a bucket over the sort's capacity: halve the buckets
+                continue
+            _lib.check(rc)
+            break
+        if int(out[0]) != npos:
+            raise RuntimeError("the export wrote %d positions, the census counted %d" % (int(out[0]), npos))
+        kb = int(out[1])
+        head, _, _, _, total = db.tk_header(wb, kb, b, npos)
+        stage = torch.empty(max(16, min(int(chunk), max(d.numel() * 8, npos * kb))), dtype=torch.uint8,
+                            pin_memory=True)
+        host = stage.numpy()
+        tmp = path + ".tmp"
+        with open(tmp, "wb") as fh:
+            fh.write(head)
+            for t in (d, keys[:npos * kb], words[:npos * wb]):  # the sections, in file order
+                flat = t.view(torch.uint8).reshape(-1)
+                for a in range(0, flat.numel(), stage.numel()):
+                    part = flat[a:a + stage.numel()]
+                    stage[:part.numel()].copy_(part)
+                    fh.write(host[:part.numel()].data)
+        os.replace(tmp, path)
+        return {"path": path, "bytes": total, "positions": npos, "word_bytes": wb, "key_bytes": kb,
+                "bucket_bits": b}
+
     def dump(self):
         """(keys u64, value u8, remoteness u32) for every reachable
         position."""

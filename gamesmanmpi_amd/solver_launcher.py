@@ -118,15 +118,15 @@ def build_parser():
                         "and by level (Win Lose Tie Draw Total per row; Solver.census) and "
                         "the longest win / loss / tie; with --json, a `census` object too")
     p.add_argument("--tablebase", action="store_true",
-                   help="with -sd, one-GPU solves of indexed games (four_to_one, sum_four_to_one, "
-                        "toot_and_otto_bitstring): write the indexed tablebase solution.gmtb "
-                        "(exported on the GPU, read by mmap: gamesmanmpi_amd.db) instead of "
-                        "solution.npz")
+                   help="with -sd, one-GPU descriptor solves: write a tablebase exported on the "
+                        "GPU and read by mmap (gamesmanmpi_amd.db) instead of solution.npz -- the "
+                        "indexed solution.gmtb for four_to_one, sum_four_to_one and "
+                        "toot_and_otto_bitstring, the keyed solution.gmtk for the other games")
     return p
 
 
 def check_tablebase_args(args, world, spec=None, descriptor=True):
-    """--tablebase writes one table from one GPU, for a game with an index."""
+    """--tablebase writes one table from one GPU, for a descriptor game."""
     if not args.tablebase:
         return
     if not args.statsdir:
@@ -135,26 +135,32 @@ def check_tablebase_args(args, world, spec=None, descriptor=True):
         raise SystemExit("--tablebase: one-GPU solves only (%d ranks: every rank's table is a shard)" % world)
     if not descriptor or args.layout == "graph":
         raise SystemExit("--tablebase: the game file needs a device descriptor (graph solves keep solution.npz)")
-    if spec is not None:
-        from gamesmanmpi_amd import _lib
-        try:
-            spec.tb_index_space()
-        except _lib.GmError:
-            raise SystemExit("--tablebase: %s has no tablebase index (keyed games without a rank function "
-                             "keep solution.npz)" % spec.name)
 
 
 def write_tablebase_stats(statsdir, spec, solver, result):
-    """<statsdir>/stats/0/solution.gmtb (+ meta.json, "format": "gmtb")."""
+    """<statsdir>/stats/0/solution.gmtb (+ meta.json, "format": "gmtb") for a
+    game with a tablebase index; solution.gmtk ("format": "gmtk"), the keyed
+    tablebase, for the descriptor games without one."""
+    from gamesmanmpi_amd import _lib
     d = os.path.join(statsdir, "stats", "0")
     os.makedirs(d, exist_ok=True)
-    info = solver.export_tablebase(os.path.join(d, "solution.gmtb"))
+    try:
+        spec.tb_index_space()
+        fmt = "gmtb"
+    except _lib.GmError:
+        fmt = "gmtk"
+    if fmt == "gmtb":
+        info = solver.export_tablebase(os.path.join(d, "solution.gmtb"))
+    else:
+        info = solver.export_keyed_tablebase(os.path.join(d, "solution.gmtk"))
+    meta = {"game": spec.name, "params": spec.params,
+            "root": result.root_line, "positions": info["positions"],
+            "owned_by_rank": 0, "format": fmt, "word_bytes": info["word_bytes"],
+            "value_codes": {"WIN": 0, "LOSS": 1, "TIE": 2, "DRAW": 3}}
+    if fmt == "gmtk":
+        meta.update(key_bytes=info["key_bytes"], bucket_bits=info["bucket_bits"])
     with open(os.path.join(d, "meta.json"), "w") as f:
-        json.dump({"game": spec.name, "params": spec.params,
-                   "root": result.root_line, "positions": info["positions"],
-                   "owned_by_rank": 0, "format": "gmtb", "word_bytes": info["word_bytes"],
-                   "value_codes": {"WIN": 0, "LOSS": 1, "TIE": 2, "DRAW": 3}},
-                  f, indent=1)
+        json.dump(meta, f, indent=1)
 
 
 def check_analysis_args(args, world, descriptor=True):

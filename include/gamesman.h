@@ -396,6 +396,48 @@ int gm_solver_export(gm_solver *s, uint32_t how, uint64_t first, uint64_t count,
                      uint32_t word_bytes, uint64_t *bits_dev,
                      uint32_t *block_counts_dev, void *words_dev,
                      uint64_t words_cap, uint64_t *n_words);
+/* ---- the keyed tablebase (solution.gmtk) ------------
+ * For the games without a tablebase index (tic_tac_toe_np, mttt,
+ * othello_bit_new; any other descriptor game works too): every position's
+ * key, truncated to the bytes that hold the largest, and its compact word,
+ * grouped by bucket = the top bucket_bits bits of gm_mix64(key) (bucket 0
+ * when bucket_bits is 0) and sorted by key inside a bucket.  A directory of
+ * 2^bucket_bits + 1 cumulative counts finds a bucket; a lookup binary-searches
+ * that one bucket.  Replaces, for those games, walking the resolved / remote
+ * shelves to save a solution (src/cache_dict.py:38-60).
+ *
+ * out[i] = the 64-bit hash of keys[i] (the splitmix64 finaliser the device
+ * uses; a bijection).  Host only, no GPU needed. */
+int gm_mix64(const uint64_t *keys, size_t n, uint64_t *out);
+/* The finished solve as keyed tablebase sections, written on the device:
+ *   stage_dev  caller-owned scratch, cap * 12 bytes, 8-byte aligned
+ *   dir_dev    2^bucket_bits + 1 u64: dir[h] = positions in buckets below h,
+ *              dir[2^bucket_bits] = positions
+ *   keys_dev   room for cap * 8 bytes, 16-byte aligned; written: positions *
+ *              key_bytes, the low key_bytes bytes of each key, by bucket, then
+ *              by key ascending
+ *   words_dev  room for cap * word_bytes bytes, 16-byte aligned: the words
+ *              (value | remoteness << 2, as gm_solver_query) truncated to
+ *              word_bytes (1, 2 or 4), in the keys' order
+ *   out        host: out[0] = positions written, out[1] = key_bytes (the
+ *              bytes that hold the OR of all keys, at least 1), out[2] = the
+ *              largest bucket, out[3] = the largest remoteness
+ * bucket_bits <= 32.  A bucket holds at most 1,024 positions: GM_EFULL when
+ * the largest (out[2]) holds more -- gm_last_error says to raise bucket_bits
+ * -- and when cap is short (out[0] = the count needed); either way the
+ * directory is complete and nothing else is written.  GM_EINVAL when a word
+ * does not fit word_bytes (gm_last_error names the remoteness), for a shard
+ * and for a solver without a finished full solve; GM_ECORRUPT for a reachable
+ * position without a word.  Synchronous on the solver's stream; reads the
+ * table only; the bytes depend on the table and bucket_bits alone.  Every
+ * layout goes through its position enumerator and the query path, except
+ * BUCKETED, whose key and word arrays are read side by side; how =
+ * GM_EXPORT_GENERIC takes BUCKETED through the query path too (A/B runs,
+ * tests). */
+int gm_solver_export_keyed(gm_solver *s, uint32_t how, uint32_t bucket_bits,
+                           uint32_t word_bytes, void *stage_dev,
+                           uint64_t *dir_dev, void *keys_dev, void *words_dev,
+                           uint64_t cap, uint64_t out[4]);
 /* change GM_F_* flags of an existing solver (e.g. kernel timing) */
 int gm_solver_set_flags(gm_solver *s, uint32_t flags);
 /* Level-granular stop / resume (checkpoints; SURVEY.md §8f rank 2 -- the
