@@ -107,8 +107,10 @@ static bool bk_ranges(u64 n, uint32_t* pshift, uint32_t* fb) {
 }
 // the bucketed kernels' instantiation for a descriptor (fixed_kind: the
 // compile-time toot boards where one exists)
+// (kernels that never generate children -- k_bk_reduce, k_bks_ownbin -- take
+// bk_dispatch_plain: the symmetric kinds differ in `children` alone)
 template <class Fn>
-static void bk_dispatch(const Desc& d, Fn&& fn) {
+static void bk_dispatch_plain(const Desc& d, Fn&& fn) {
   switch (fixed_kind(d)) {
     case K_TTT: fn(std::integral_constant<int, K_TTT>{}); break;
     case K_TOOT_6x4: fn(std::integral_constant<int, K_TOOT_6x4>{}); break;
@@ -118,8 +120,20 @@ static void bk_dispatch(const Desc& d, Fn&& fn) {
     default: fn(std::integral_constant<int, K_OTHELLO>{}); break;
   }
 }
+template <class Fn>
+static void bk_dispatch(const Desc& d, Fn&& fn) {
+  if (!d.bsym) return bk_dispatch_plain(d, fn);
+  bk_dispatch_plain(d, [&](auto kind_) {  // children as orbit representatives (gm_sym.h)
+    fn(std::integral_constant<int, decltype(kind_)::value | K_SYM>{});
+  });
+}
 #define BK_KIND_LAUNCH(KERNEL, GRID, BLOCK, S, ...)                                                      \
   bk_dispatch((S)->d, [&](auto kind_) {                                                                  \
+    constexpr int K_ = decltype(kind_)::value;                                                           \
+    hipLaunchKernelGGL(KERNEL<K_>, dim3(GRID), dim3(BLOCK), 0, (S)->stream, __VA_ARGS__);               \
+  })
+#define BK_KIND_LAUNCH_PLAIN(KERNEL, GRID, BLOCK, S, ...)                                                      \
+  bk_dispatch_plain((S)->d, [&](auto kind_) {                                                                  \
     constexpr int K_ = decltype(kind_)::value;                                                           \
     hipLaunchKernelGGL(KERNEL<K_>, dim3(GRID), dim3(BLOCK), 0, (S)->stream, __VA_ARGS__);               \
   })
@@ -452,10 +466,10 @@ static int solve_bucketed(gm_solver* s, gm_result* out) {
         ap = (uint32_t*)s->S2k;
         nbwd++;
       }
-      BK_KIND_LAUNCH(k_bk_reduce, gr, kBkReduceThreads, s, s->d, s->bkK + P.lb, P.n, ap, rfo, P.fb, Fp - 1, NR,
+      BK_KIND_LAUNCH_PLAIN(k_bk_reduce, gr, kBkReduceThreads, s, s->d, s->bkK + P.lb, P.n, ap, rfo, P.fb, Fp - 1, NR,
                      s->bkW + P.lb, s->st);
     } else {
-      BK_KIND_LAUNCH(k_bk_reduce, gr, kBkReduceThreads, s, s->d, s->bkK + P.lb, P.n, (const uint32_t*)nullptr,
+      BK_KIND_LAUNCH_PLAIN(k_bk_reduce, gr, kBkReduceThreads, s, s->d, s->bkK + P.lb, P.n, (const uint32_t*)nullptr,
                      (const uint32_t*)nullptr, P.fb, 0u, NR, s->bkW + P.lb, s->st);
     }
     nbwd++;

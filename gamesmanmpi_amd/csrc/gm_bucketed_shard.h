@@ -521,7 +521,7 @@ static int run_bucketed_shards(std::vector<gm_solver*> ss, gm_result* out) {
       hipLaunchKernelGGL(k_bk_scan, dim3(1), dim3(1024), 0, s->stream, s->ucnt, NB, cst, s->bktotal);
       HIPCHK(hipMemsetAsync(s->bkgc, 0, (2 * kBkC + 4) * 4, s->stream));
       const uint32_t capd = (uint32_t)(s->Emax / (u64)W);
-      bk_dispatch(s->d, [&](auto kind_) {
+      bk_dispatch_plain(s->d, [&](auto kind_) {
         constexpr int K_ = decltype(kind_)::value;
         hipLaunchKernelGGL((k_bks_ownbin<K_>), dim3(kBkC), dim3(kBkStreamThreads), 0, s->stream, s->d, (const u64*)s->S1k,
                            (const uint32_t*)fo, (const uint32_t*)cst, NB, F, (uint32_t)W, (uint32_t)s->rank << 29, capd,
@@ -979,7 +979,7 @@ static int run_bucketed_shards(std::vector<gm_solver*> ss, gm_result* out) {
                              10u + P.fb, Fp, K, s->bkcur + kBkC, (uint32_t*)s->S2k);
           ap = (uint32_t*)s->S2k;
         }
-        BK_KIND_LAUNCH(k_bk_reduce, gr, kBkReduceThreads, s, s->d, s->bkK + P.lb, P.n, ap, rfo, P.fb, Fp - 1, NR,
+        BK_KIND_LAUNCH_PLAIN(k_bk_reduce, gr, kBkReduceThreads, s, s->d, s->bkK + P.lb, P.n, ap, rfo, P.fb, Fp - 1, NR,
                        s->bkW + P.lb, s->st);
       } else if (edges && P.eout) {
         const uint32_t* rfo = s->meta + P.rfo_off;
@@ -999,10 +999,10 @@ static int run_bucketed_shards(std::vector<gm_solver*> ss, gm_result* out) {
                              10u + P.fb, Fp, K, s->bkcur + kBkC, (uint32_t*)s->S2k);
           ap = (uint32_t*)s->S2k;
         }
-        BK_KIND_LAUNCH(k_bk_reduce, gr, kBkReduceThreads, s, s->d, s->bkK + P.lb, P.n, ap, rfo, P.fb, Fp - 1, NR,
+        BK_KIND_LAUNCH_PLAIN(k_bk_reduce, gr, kBkReduceThreads, s, s->d, s->bkK + P.lb, P.n, ap, rfo, P.fb, Fp - 1, NR,
                        s->bkW + P.lb, s->st);
       } else {
-        BK_KIND_LAUNCH(k_bk_reduce, gr, kBkReduceThreads, s, s->d, s->bkK + P.lb, P.n, (const uint32_t*)nullptr,
+        BK_KIND_LAUNCH_PLAIN(k_bk_reduce, gr, kBkReduceThreads, s, s->d, s->bkK + P.lb, P.n, (const uint32_t*)nullptr,
                        (const uint32_t*)nullptr, P.fb, 0u, NR, s->bkW + P.lb, s->st);
       }
       HIPCHK(hipGetLastError());

@@ -82,6 +82,12 @@ struct Desc {
   // canonical representatives of their orbit under the game module's
   // symmetry_functions() (othello_bit_new.py:224-226: player_flip, order 2)
   int sym;
+  // board symmetry (params "board_symmetry=1"; gm_sym.h): keys are the
+  // smallest image under the game's board group.  K_TOOT: the mirror's
+  // delta-swap masks, swap i exchanging bit i and bit L-1-i of every row
+  int bsym;
+  int nmir;
+  uint64_t mir[12];
 };
 
 // Which part of a DENSE table's global prefix space one table holds, and
@@ -175,6 +181,10 @@ GM_HD int popc64(uint64_t v) {
 #endif
 }
 
+}  // namespace gm
+#include "gm_sym.h"
+namespace gm {
+
 // ---------------------------------------------------------------------------
 // Sum of Four-To-One heaps (four_to_one.py:7-22 per heap;
 // gamesmanmpi_amd/games/sum_four_to_one.py).  key = mixed-radix rank, heap 0
@@ -245,6 +255,12 @@ GM_HD int ttt_children(const Desc&, uint64_t k, F&& emit) {
     if (!(((a | b) >> c) & 1)) { emit(k | (who << (2 * c)), 1); n++; }
   return n;
 }
+// the same children as orbit representatives (board_symmetry=1): its own
+// function, so that the plain emit above carries no test
+template <class F>
+GM_HD int ttt_children_sym(const Desc& d, uint64_t k, F&& emit) {
+  return ttt_children(d, k, [&](uint64_t c, int step) { emit(sym_ttt_canon(c), step); });
+}
 GM_HD int ttt_level(const Desc&, uint64_t k) {
   return popc64(ttt_plane(k, 1) | ttt_plane(k, 2));
 }
@@ -292,6 +308,10 @@ GM_HD int toot_children(const Desc& d, uint64_t k, F&& emit) {
     if (nO > 0) { emit((k - (1ull << (hb + 3))) ^ turn ^ (cell << A), 1); n++; }
   }
   return n;
+}
+template <class F>
+GM_HD int toot_children_sym(const Desc& d, uint64_t k, F&& emit) {
+  return toot_children(d, k, [&](uint64_t c, int step) { emit(sym_toot_canon(d, c), step); });
 }
 GM_HD int toot_level(const Desc& d, uint64_t k) {
   return popc64((k | (k >> d.A)) & d.full);
@@ -365,6 +385,13 @@ struct TootFixed {
       if (hasO) { emit(kO ^ (cell << A), 1); n++; }
     }
     return n;
+  }
+  // the left-right mirror with compile-time masks, and the children as
+  // orbit representatives (board_symmetry=1)
+  static GM_HD uint64_t mirror(uint64_t k) { return sym_toot_mirror_fixed<L, H>(k); }
+  template <class F>
+  static GM_HD int children_sym(const Desc& d, uint64_t k, F&& emit) {
+    return children(d, k, [&](uint64_t c, int step) { emit(sym_min(c, mirror(c)), step); });
   }
   static GM_HD int level(const Desc&, uint64_t k) { return popc64((k | (k >> A)) & full); }
 };
@@ -447,6 +474,10 @@ GM_HD int oth_children(const Desc& d, uint64_t k, F&& emit) {
   }
   return n;
 }
+template <class F>
+GM_HD int oth_children_sym(const Desc& d, uint64_t k, F&& emit) {
+  return oth_children(d, k, [&](uint64_t c, int step) { emit(sym_oth_canon(d, c), step); });
+}
 GM_HD int oth_level(const Desc& d, uint64_t k) {
   return popc64((k | (k >> d.A)) & d.full) - 4 + (int)((k >> (2 * d.A + 1)) & 3);
 }
@@ -487,6 +518,32 @@ template <> struct Game<K_OTHELLO> {
   static GM_HD int level(const Desc& d, uint64_t k) { return oth_level(d, k); }
 };
 
+// the kinds of a board-symmetric descriptor (Desc::bsym): the same rules,
+// children emitted as orbit representatives.  Instantiations of their own,
+// so that a solve without the parameter runs the kernels it always ran.
+constexpr int K_SYM = 256;
+constexpr int kind_base(int kind) { return kind & ~K_SYM; }
+template <> struct Game<K_TTT | K_SYM> : Game<K_TTT> {
+  template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return ttt_children_sym(d, k, f); }
+};
+template <> struct Game<K_TOOT | K_SYM> : Game<K_TOOT> {
+  template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return toot_children_sym(d, k, f); }
+};
+template <> struct Game<K_TOOT_6x4 | K_SYM> : Game<K_TOOT_6x4> {
+  template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return children_sym(d, k, f); }
+};
+template <> struct Game<K_TOOT_5x4 | K_SYM> : Game<K_TOOT_5x4> {
+  template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return children_sym(d, k, f); }
+};
+template <> struct Game<K_TOOT_4x4 | K_SYM> : Game<K_TOOT_4x4> {
+  template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return children_sym(d, k, f); }
+};
+template <> struct Game<K_OTHELLO | K_SYM> : Game<K_OTHELLO> {
+  template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return oth_children_sym(d, k, f); }
+};
+// the instantiation id with the symmetric form where the descriptor asks
+GM_HD int sym_kind(const Desc& d, int kind) { return d.bsym ? (kind | K_SYM) : kind; }
+
 GM_HD int any_prim(const Desc& d, uint64_t k) {
   switch (d.kind) {
     case K_SUM: return sum_prim(d, k);
@@ -497,6 +554,11 @@ GM_HD int any_prim(const Desc& d, uint64_t k) {
 }
 template <class F>
 GM_HD int any_children(const Desc& d, uint64_t k, F&& f) {
+  if (d.bsym) switch (d.kind) {
+    case K_TTT: return ttt_children_sym(d, k, f);
+    case K_TOOT: return toot_children_sym(d, k, f);
+    default: return oth_children_sym(d, k, f);
+  }
   switch (d.kind) {
     case K_SUM: return sum_children(d, k, f);
     case K_TTT: return ttt_children(d, k, f);
@@ -505,7 +567,10 @@ GM_HD int any_children(const Desc& d, uint64_t k, F&& f) {
   }
 }
 // canonical key of any position (identity without symmetry hooks)
-GM_HD uint64_t any_canon(const Desc& d, uint64_t k) { return d.kind == K_OTHELLO ? oth_canon(d, k) : k; }
+GM_HD uint64_t any_canon(const Desc& d, uint64_t k) {
+  if (d.bsym) return sym_board_canon(d, k);
+  return d.kind == K_OTHELLO ? oth_canon(d, k) : k;
+}
 GM_HD int any_level(const Desc& d, uint64_t k) {
   switch (d.kind) {
     case K_SUM: return sum_level(d, k);

@@ -172,8 +172,7 @@ __device__ __forceinline__ uint32_t owner_dev(const Desc& d, u64 key, uint32_t P
 // occupancy)
 template <int KIND>
 __device__ __forceinline__ uint32_t owner_k(const Desc& d, u64 key, uint32_t P) {
-  if constexpr (KIND == K_TTT || KIND == K_TOOT || KIND == K_OTHELLO || KIND == K_TOOT_6x4 || KIND == K_TOOT_5x4 ||
-                KIND == K_TOOT_4x4)
+  if constexpr (kind_base(KIND) != K_SUM)  // the board games, plain or symmetric
     return owner_fast(d, key, P);
   else
     return owner_dev(d, key, P);
@@ -187,8 +186,7 @@ __device__ __noinline__ uint32_t owner_fast_call(const OwnerGeom d, u64 key, uin
 // as a call, for a kernel specialised to KIND (no scratch-array path for the fast kinds)
 template <int KIND>
 __device__ __forceinline__ uint32_t owner_call_k(const Desc& d, u64 key, uint32_t P) {
-  if constexpr (KIND == K_TTT || KIND == K_TOOT || KIND == K_OTHELLO || KIND == K_TOOT_6x4 || KIND == K_TOOT_5x4 ||
-                KIND == K_TOOT_4x4)
+  if constexpr (kind_base(KIND) != K_SUM)  // the board games, plain or symmetric
     return owner_fast_call(OwnerGeom{d.kind, d.variant, d.A, d.nbits}, key, P);
   else
     return owner_of_call(d, key, P);

@@ -988,6 +988,7 @@ static int rank_shape(const Desc* d, RankShape* rs) {
 }
 
 static bool rank_ok(const Desc* d) {
+  if (d->bsym) return false;  // the RANKED index has no representative form (board_symmetry=1)
   if (d->kind != K_TOOT || d->L < 1 || d->L > kRankMaxCols || d->H < 1 || d->H > 7) return false;
   if (d->max_levels > 64 || (int)d->max_levels != d->L * d->H + 1) return false;  // remoteness in 6 bits
   double n = 8;

@@ -329,6 +329,25 @@ static int build_desc(const char* name, const char* params, Desc* out) {
   }
   if (kv(params, "symmetry", 0) && d.kind != K_OTHELLO)
     return fail(GM_EINVAL, "'%s' defines no symmetry_functions() to reduce by", name);
+  if (kv(params, "board_symmetry", 0)) {  // orbit representatives under the board's group (gm_sym.h)
+    if (d.kind == K_SUM)
+      return fail(GM_EINVAL, "'%s' has no board: board_symmetry=1 covers tic-tac-toe, toot-and-otto and othello "
+                             "(heap permutations are not implemented)", name);
+    if (kv(params, "symmetry", 0))
+      return fail(GM_EINVAL, "board_symmetry=1 and symmetry=1 do not combine: player_flip swaps the colours "
+                             "the board maps keep");
+    d.bsym = 1;
+    if (d.kind == K_TOOT) {
+      d.nmir = d.L / 2;
+      for (int i = 0; i < d.nmir; i++) d.mir[i] = sym_toot_mask(d.L, d.H, i);
+    }
+    // every map fixes the start position, so the group acts on the reachable
+    // set and the root is its own representative
+    for (int i = 0; i < sym_board_maps(d); i++)
+      if (sym_board_map(d, d.root, i) != d.root)
+        return fail(GM_EINVAL, "board map %d of '%s' moves the start position of this board", i, name);
+    if (sym_board_canon(d, d.root) != d.root) return fail(GM_EINVAL, "the root of '%s' is not its own representative", name);
+  }
   *out = d;
   return 0;
 }
@@ -1203,6 +1222,11 @@ static void enqueue_level_resolve(gm_solver* s, int L) {
                      s->lcap, s->st, L);
 }
 static void do_expand(gm_solver* s, int L) {
+  if (s->d.bsym) switch (s->d.kind) {  // children as orbit representatives (gm_sym.h)
+    case K_TTT: return enqueue_level_expand<K_TTT | K_SYM>(s, L);
+    case K_TOOT: return enqueue_level_expand<K_TOOT | K_SYM>(s, L);
+    default: return enqueue_level_expand<K_OTHELLO | K_SYM>(s, L);
+  }
   switch (s->d.kind) {
     case K_SUM: enqueue_level_expand<K_SUM>(s, L); break;
     case K_TTT: enqueue_level_expand<K_TTT>(s, L); break;
@@ -1211,6 +1235,11 @@ static void do_expand(gm_solver* s, int L) {
   }
 }
 static void do_resolve(gm_solver* s, int L) {
+  if (s->d.bsym) switch (s->d.kind) {
+    case K_TTT: return enqueue_level_resolve<K_TTT | K_SYM>(s, L);
+    case K_TOOT: return enqueue_level_resolve<K_TOOT | K_SYM>(s, L);
+    default: return enqueue_level_resolve<K_OTHELLO | K_SYM>(s, L);
+  }
   switch (s->d.kind) {
     case K_SUM: enqueue_level_resolve<K_SUM>(s, L); break;
     case K_TTT: enqueue_level_resolve<K_TTT>(s, L); break;
@@ -1499,11 +1528,24 @@ int gm_host_level(int game, const uint64_t* keys, size_t n, int32_t* levels) {
   return 0;
 }
 
+int gm_symmetry_count(int game, uint32_t* count) {
+  const Desc* d = get_game(game);
+  if (!d || !count) return fail(GM_EINVAL, "bad argument");
+  *count = d->bsym ? (uint32_t)sym_board_maps(*d) : d->sym ? 1u : 0u;
+  return 0;
+}
+
 int gm_symmetry(int game, int which, const uint64_t* keys, size_t n, uint64_t* out) {
   const Desc* d = get_game(game);
   if (!d || (n && (!keys || !out))) return fail(GM_EINVAL, "bad argument");
   if (which == -1) {
     for (size_t i = 0; i < n; i++) out[i] = any_canon(*d, keys[i]);
+    return 0;
+  }
+  if (d->bsym) {
+    if (which < 0 || which >= sym_board_maps(*d))
+      return fail(GM_EINVAL, "no board map %d for this game (%d maps)", which, sym_board_maps(*d));
+    for (size_t i = 0; i < n; i++) out[i] = sym_board_map(*d, keys[i], which);
     return 0;
   }
   if (which != 0 || d->kind != K_OTHELLO) return fail(GM_EINVAL, "no symmetry function %d for this game", which);
@@ -1721,6 +1763,7 @@ int gm_plan_keyed_shard(int game, int rank, int world, uint64_t positions, uint3
   if (world < 2 || world > 8 || rank < 0 || rank >= world) return fail(GM_EINVAL, "bad shard %d/%d (2..8 ranks)", rank, world);
   if (flags & GM_F_RANKED_SHARD) {  // the RANKED index space, md5-owned slots (gm_ranked_shard.h)
     memset(out, 0, sizeof *out);
+    if (d->bsym) return fail(GM_EINVAL, "board_symmetry=1 has no ranked layout: the RANKED index has no representative form");
     return plan_ranked_shard(d, world, max_table_bytes, out);
   }
   if (!bk_ok(d) || (flags & GM_F_HASH_TABLE))
@@ -1769,6 +1812,7 @@ int gm_solver_create_shard(int game, int rank, int world, const gm_buffers* buf,
     if (world != 1 && !(buf->flags & GM_F_RANKED_SHARD))
       return fail(GM_EINVAL, "ranked md5 shards are planned with GM_F_RANKED_SHARD (gm_plan_keyed_shard)");
     if (world > 8 || rank < 0 || rank >= world) return fail(GM_EINVAL, "bad ranked shard %d/%d (2..8 ranks)", rank, world);
+    if (d->bsym) return fail(GM_EINVAL, "board_symmetry=1 has no ranked layout: the RANKED index has no representative form");
     if (!rank_ok(d)) return fail(GM_EINVAL, "game has no ranked layout");
   } else if (buf->mode == GM_MODE_BUCKETED) {
     if (world < 1 || rank < 0 || rank >= world) return fail(GM_EINVAL, "bad shard %d/%d", rank, world);
@@ -2439,12 +2483,25 @@ int gm_owner(int game, const uint64_t* keys_dev, uint64_t n, int world_size, uin
 // md5-sharded keyed tables (gm_keyed_shard.h): the host moves keys/words
 // between ranks between these steps (gamesmanmpi_amd/keyed.py)
 // ---------------------------------------------------------------------------
-#define GM_KIND_DISPATCH(KERNEL, GRID, S, ...)                                                      \
-  switch ((S)->d.kind) {                                                                           \
-    case K_SUM: hipLaunchKernelGGL(KERNEL<K_SUM>, dim3(GRID), dim3(kBlock), 0, (S)->stream, __VA_ARGS__); break; \
-    case K_TTT: hipLaunchKernelGGL(KERNEL<K_TTT>, dim3(GRID), dim3(kBlock), 0, (S)->stream, __VA_ARGS__); break; \
-    case K_TOOT: hipLaunchKernelGGL(KERNEL<K_TOOT>, dim3(GRID), dim3(kBlock), 0, (S)->stream, __VA_ARGS__); break; \
-    default: hipLaunchKernelGGL(KERNEL<K_OTHELLO>, dim3(GRID), dim3(kBlock), 0, (S)->stream, __VA_ARGS__); break; \
+#define GM_KIND_CASE(KERNEL, K, GRID, S, ...) \
+  case K: hipLaunchKernelGGL(KERNEL<K>, dim3(GRID), dim3(kBlock), 0, (S)->stream, __VA_ARGS__); break;
+#define GM_KIND_DISPATCH(KERNEL, GRID, S, ...)                        \
+  switch (sym_kind((S)->d, (S)->d.kind)) {                           \
+    GM_KIND_CASE(KERNEL, K_SUM, GRID, S, __VA_ARGS__)                 \
+    GM_KIND_CASE(KERNEL, K_TTT, GRID, S, __VA_ARGS__)                 \
+    GM_KIND_CASE(KERNEL, K_TOOT, GRID, S, __VA_ARGS__)                \
+    GM_KIND_CASE(KERNEL, K_OTHELLO, GRID, S, __VA_ARGS__)             \
+    GM_KIND_CASE(KERNEL, K_TTT | K_SYM, GRID, S, __VA_ARGS__)         \
+    GM_KIND_CASE(KERNEL, K_TOOT | K_SYM, GRID, S, __VA_ARGS__)        \
+    GM_KIND_CASE(KERNEL, K_OTHELLO | K_SYM, GRID, S, __VA_ARGS__)     \
+  }
+// kernels that never generate children (k_ks_insert, k_ks_reduce)
+#define GM_KIND_DISPATCH_PLAIN(KERNEL, GRID, S, ...)                  \
+  switch ((S)->d.kind) {                                             \
+    GM_KIND_CASE(KERNEL, K_SUM, GRID, S, __VA_ARGS__)                 \
+    GM_KIND_CASE(KERNEL, K_TTT, GRID, S, __VA_ARGS__)                 \
+    GM_KIND_CASE(KERNEL, K_TOOT, GRID, S, __VA_ARGS__)                \
+    GM_KIND_CASE(KERNEL, K_OTHELLO, GRID, S, __VA_ARGS__)             \
   }
 
 static int ks_check(gm_solver* s, int level) {
@@ -2519,7 +2576,7 @@ int gm_ks_insert(gm_solver* s, int level, const uint64_t* keys_dev, uint64_t n) 
   int rc = ks_check(s, level);
   if (rc) return rc;
   if (n && !keys_dev) return fail(GM_EINVAL, "null keys");
-  if (n) GM_KIND_DISPATCH(k_ks_insert, ks_grid(s, n), s, s->d, s->tab, s->mask, s->lv, s->lcap, s->st, level,
+  if (n) GM_KIND_DISPATCH_PLAIN(k_ks_insert, ks_grid(s, n), s, s->d, s->tab, s->mask, s->lv, s->lcap, s->st, level,
                           (const u64*)keys_dev, (u64)n);
   HIPCHK(hipGetLastError());
   return 0;
@@ -2567,7 +2624,7 @@ int gm_ks_reduce(gm_solver* s, int level, const uint64_t* offsets_dev, const uin
   if ((rc = gm_ks_level_size(s, level, &width))) return rc;
   if (!width) return 0;
   if (!offsets_dev || !child_words_dev) return fail(GM_EINVAL, "bad argument");
-  GM_KIND_DISPATCH(k_ks_reduce, ks_grid(s, width), s, s->d, s->tab, s->mask, s->lv, s->lcap, s->st, level,
+  GM_KIND_DISPATCH_PLAIN(k_ks_reduce, ks_grid(s, width), s, s->d, s->tab, s->mask, s->lv, s->lcap, s->st, level,
                    offsets_dev, child_words_dev);
   HIPCHK(hipGetLastError());
   return ks_errors(s);

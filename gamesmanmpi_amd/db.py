@@ -386,7 +386,11 @@ class KeyedTablebase:
     def lookup_keys(self, keys):
         """uint32 words (value | remoteness << 2) of packed u64 keys; NO_WORD
         for a key the table does not hold.  One bucket range per query, then
-        ceil(log2(largest range + 1)) binary-search steps over all of them."""
+        ceil(log2(largest range + 1)) binary-search steps over all of them.
+        Opened with a symmetric GameSpec (symmetry=1 / board_symmetry=1), the
+        keys are mapped to their orbit representatives first."""
+        if self.spec is not None and self.spec.symmetric:
+            keys = self.spec.symmetry(keys)
         q = np.ascontiguousarray(keys, dtype=np.uint64)
         out = np.full(len(q), NO_WORD, np.uint32)
         ok = np.ones(len(q), bool)
@@ -432,7 +436,12 @@ class SolutionDB:
             with open(os.path.join(os.path.dirname(tk), "meta.json")) as f:
                 self.meta = json.load(f)
             self.by, self.ranks = "key", 1
-            self.tablebase = KeyedTablebase(tk)
+            spec = None
+            params = self.meta.get("params", "").split(",")
+            if "game" in self.meta and ("symmetry=1" in params or "board_symmetry=1" in params):
+                from .games import GameSpec  # a symmetric table's spec is its key map
+                spec = GameSpec(self.meta["game"], self.meta["params"])
+            self.tablebase = KeyedTablebase(tk, spec)
             return
         if os.path.exists(tb):
             # an indexed tablebase (one-GPU solves of indexed games): mapped, not loaded
@@ -497,8 +506,10 @@ class SolutionDB:
         if spec is None:
             raise ValueError("a keyed table needs the game's GameSpec")
         key = spec.key_of(pos)
-        if "symmetry=1" in self.meta.get("params", "").split(","):
-            # a symmetric solve stored orbit representatives (gm_symmetry)
+        params = self.meta.get("params", "").split(",")
+        if "symmetry=1" in params or "board_symmetry=1" in params:
+            # a symmetric solve stored orbit representatives (gm_symmetry);
+            # npz tables and both tablebase readers are looked up through here
             from .games import GameSpec
             key = int(GameSpec(spec.name, self.meta["params"]).symmetry(
                 np.array([key], np.uint64))[0])
@@ -613,6 +624,12 @@ def convert_to_tablebase(root, spec):
     if db.by != "key":
         raise ValueError("graph tables (by position name) have no index")
     from . import _lib
+    from .games import GameSpec
+    # the format follows the TABLE's own params, not the game file's: a
+    # symmetric solve (symmetry=1 / board_symmetry=1) holds representatives
+    # only and has no index, whatever the plain game has
+    if "params" in db.meta:
+        spec = GameSpec(db.meta.get("game", spec.name), db.meta["params"])
     try:
         space = spec.tb_index_space()
     except _lib.GmError:

@@ -47,15 +47,31 @@ class GameSpec:
     def __repr__(self):
         return "GameSpec(%r, %r)" % (self.name, self.params)
 
-    # -- symmetry hooks (params "symmetry=1") ------------------------------
+    # -- symmetry hooks (params "symmetry=1" / "board_symmetry=1") ----------
     @property
     def symmetric(self):
-        return any(p.strip() == "symmetry=1" for p in self.params.split(","))
+        """The table holds orbit representatives: under the module's own
+        symmetry_functions() (symmetry=1) or the board's maps
+        (board_symmetry=1)."""
+        return self.board_symmetric or any(p.strip() == "symmetry=1" for p in self.params.split(","))
+
+    @property
+    def board_symmetric(self):
+        return any(p.strip() == "board_symmetry=1" for p in self.params.split(","))
+
+    def symmetry_count(self):
+        """Number of maps `symmetry(keys, which)` accepts as `which`
+        (include/gamesman.h gm_symmetry_count; 0 without a symmetry
+        parameter)."""
+        n = _lib.ctypes.c_uint32()
+        _lib.check(_lib.load().gm_symmetry_count(self.id, _lib.ctypes.byref(n)))
+        return n.value
 
     def symmetry(self, keys, which=-1):
         """which=-1: canonical orbit representatives of `keys` (identity
         for specs without symmetry); which=i: the module's i-th symmetry
-        function as a key map (include/gamesman.h gm_symmetry)."""
+        function, or with board_symmetry=1 the i-th map of the board's
+        group, as a key map (include/gamesman.h gm_symmetry)."""
         keys = np.ascontiguousarray(keys, dtype=np.uint64)
         out = np.zeros(len(keys), np.uint64)
         _lib.check(_lib.load().gm_symmetry(self.id, int(which), keys.ctypes.data,

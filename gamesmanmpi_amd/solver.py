@@ -80,6 +80,9 @@ class Solver:
         if layout not in ("auto", "planes", "dense", "hashed", "bucketed", "ranked"):
             raise ValueError("layout must be auto, planes, dense, ranked, bucketed or hashed")
         self.layout = layout
+        if layout == "ranked" and self.spec.board_symmetric:
+            raise _lib.GmError(_lib.GM_EINVAL, "board_symmetry=1 has no ranked layout: the RANKED index "
+                                               "has no representative form (use bucketed or hashed)")
         self.max_table_bytes = int(max_table_bytes)
         self.rank, self.world = int(rank), int(world)
         self.stream = stream
@@ -351,7 +354,10 @@ class Solver:
         nchild u8[n], best i8[n]) of `keys` (gm_solver_moves): each key's
         children in gen_moves() order with their words (GM_EMPTY_KEY /
         GM_NO_WORD in unused slots) and the index of the best move; a
-        primitive or unreachable key has nchild 0 and best -1."""
+        primitive or unreachable key has nchild 0 and best -1.  On a
+        symmetric table (symmetry=1 / board_symmetry=1) the children are
+        reported as the descriptor emits them: as orbit representatives, of
+        which a parent may list the same one more than once."""
         torch = self.torch
         keys = np.ascontiguousarray(keys, dtype=np.uint64)
         n, m = len(keys), _lib.GM_MAXCHILD
@@ -373,7 +379,9 @@ class Solver:
     def best_line(self, key=None, cap=None):
         """(keys u64, values u8, remoteness u32) of the optimal line from
         `key` (default: the root) to a primitive position, one kernel launch
-        (gm_solver_line); at most `cap` entries (default: one per level)."""
+        (gm_solver_line); at most `cap` entries (default: one per level).
+        On a symmetric table the line runs through orbit representatives, as
+        `moves` reports them."""
         torch = self.torch
         if key is None:
             key = self.spec.root_key

@@ -99,6 +99,12 @@ def build_parser():
                    help="solve orbit representatives under the game module's "
                         "symmetry_functions() (othello_bit_new: player_flip); "
                         "every position keeps its own value and remoteness")
+    p.add_argument("--board-symmetry", action="store_true",
+                   help="solve orbit representatives under the board maps that fix the "
+                        "start position (tic-tac-toe: the 8 maps of the square; "
+                        "toot-and-otto: the left-right mirror; othello: 180-degree turn, "
+                        "transpose, anti-transpose); prints the representative count; "
+                        "every position keeps its own value and remoteness")
     p.add_argument("-ck", "--checkpoint", metavar="DIR",
                    help="one-GPU solves: checkpoint the solver state into DIR "
                         "every --checkpoint-every levels and resume from DIR "
@@ -373,6 +379,9 @@ def main(argv=None):
         spec = spec_for_module(game, os.path.splitext(
             os.path.basename(args.game_file))[0])
     except ValueError as e:  # no device descriptor for this file
+        if args.board_symmetry:
+            raise SystemExit("--board-symmetry: %s has no device descriptor, so no board group here"
+                             % args.game_file)
         if args.layout not in ("auto", "graph"):
             raise
         check_analysis_args(args, world, descriptor=False)
@@ -380,6 +389,8 @@ def main(argv=None):
         logging.debug("%s: solving through the host-enumerated graph", e)
         return solve_generic(args, game, rank, world, local)
     if args.layout == "graph":
+        if args.board_symmetry:
+            raise SystemExit("--board-symmetry: the host-enumerated graph path (--layout graph) has no board group")
         return solve_generic(args, game, rank, world, local)
     check_tablebase_args(args, world, spec)
     if args.symmetries:
@@ -392,6 +403,20 @@ def main(argv=None):
     if not args.no_verify:
         n = spec.verify(game, samples=args.verify_samples)
         logging.debug("descriptor %r verified on %d positions", spec, n)
+    if args.board_symmetry:
+        # after the replay of the module's own rules: the parameter changes
+        # which keys the descriptor emits, not the game
+        if args.symmetries:
+            raise SystemExit("--board-symmetry and --symmetries do not combine")
+        if spec.name in DENSE_STEMS:
+            raise SystemExit("--board-symmetry: %s has no board group here (tic-tac-toe, "
+                             "toot-and-otto and othello do)" % args.game_file)
+        if args.layout == "ranked":
+            raise SystemExit("--board-symmetry: the ranked layout has no representative form")
+        from gamesmanmpi_amd.games import GameSpec
+        spec = GameSpec(spec.name, (spec.params + ",board_symmetry=1").lstrip(","))
+        if not args.no_verify:
+            spec.verify(game, samples=args.verify_samples)  # canonical children, same values
 
     if args.checkpoint and world > 1:
         raise SystemExit("-ck/--checkpoint covers one-GPU solves (a sharded solve's state spans ranks)")
@@ -460,6 +485,8 @@ def main(argv=None):
         result = solver.solve()
     if rank == 0:
         print(result.root_line, flush=True)  # src/process.py:47-52
+        if args.board_symmetry:
+            print("%d representatives" % result.positions, flush=True)
         census = device_census(spec, solver) if args.census else None
         if args.json:
             row = {"game": spec.name, "params": spec.params,

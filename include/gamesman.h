@@ -245,6 +245,26 @@ int gm_host_level(int game, const uint64_t *keys, size_t n, int32_t *levels);
  * (othello: 0 = player_flip), for checking a module against its descriptor. */
 int gm_symmetry(int game, int which, const uint64_t *keys, size_t n,
                 uint64_t *out);
+/* Board symmetry (params "board_symmetry=1"): keys are the smallest image of
+ * their orbit under the board maps that fix the start position.  Only the
+ * cell planes move; hands, turn bit, pass count and side to move stay, so a
+ * map keeps value, remoteness, level and child count.  gm_symmetry numbers
+ * the maps, identity excluded, applied right to left:
+ *   tic_tac_toe_np, mttt (cell 3x+y; R: x -> 2-x, C: y -> 2-y, T: transpose)
+ *     0 R   1 C   2 RC (180-degree turn)   3 T   4 RT   5 CT   6 RCT
+ *   toot_and_otto_bitstring   0 left-right mirror x -> length-1-x
+ *   othello_bit_new (square)  0 180-degree turn   1 transpose (x,y) -> (y,x)
+ *                             2 anti-transpose (the turn of the transpose)
+ * Refused (GM_EINVAL): four_to_one and sum_four_to_one, the combination
+ * with symmetry=1, and the RANKED layout (its index has no representative
+ * form; a toot-and-otto solve plans BUCKETED, or HASHED with
+ * GM_F_HASH_TABLE).  Children (gm_host_expand, gm_solver_moves,
+ * gm_solver_line) are reported as the descriptor emits them: as
+ * representatives, and a parent may emit the same representative twice
+ * (edges count every occurrence).
+ * gm_symmetry_count: the number of maps gm_symmetry accepts as `which` for
+ * this game and params (0 without a symmetry parameter; 1 for symmetry=1). */
+int gm_symmetry_count(int game, uint32_t *count);
 
 /* Buffer sizes for a solve of at most `positions` reachable positions
  * (0 = the game's own bound).  DENSE is chosen when the descriptor supports
