@@ -8,7 +8,7 @@
 //
 // Three kernels count, all into the same bins:
 //   k_census<EN, WF>       any layout: the position enumerators and "word of
-//                          key" functors of gm_moves.h, any_level for the level
+//                          key" functors of gm_table.h, any_level for the level
 //   k_plane_census<NO, WB> PLANES in storage order: one 16-B load = 16 (8-bit
 //                          words) or 8 (16-bit) positions of one row; value,
 //                          remoteness and level follow from where the word is
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(256) void k_plane_census(Desc d, PlaneGeom g, const
 // counts of a word's slots are summed in a register (8 bits per value) and
 // added once per word and value; the remoteness is binned per slot.  The 64
 // word bytes are read as four 16-B loads, a quarter without a reached slot
-// not at all.  (lvt: k_rk_scan's.)
+// not at all.  (lvt: RankEnum's, gm_table.h.)
 template <bool WIT>
 __global__ __launch_bounds__(256) void k_rk_census(RankGeom g, const u64* __restrict__ lvt, uint32_t T, u64 nwords,
                                                    CensusOut o) {

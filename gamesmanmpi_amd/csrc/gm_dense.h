@@ -1695,7 +1695,7 @@ __global__ void k_dense_root(DenseView v, const uint32_t* words, const u64* bits
 }
 
 // word of a key this table owns (NO_WORD for unreachable / not owned);
-// shared by k_dense_query and the move kernels (gm_moves.h)
+// DenseWords (gm_table.h)
 __device__ __forceinline__ uint32_t dense_word(const Desc& d, const DenseView& v, const uint32_t* words,
                                                const u64* bits, uint32_t wbits, u64 key) {
   u64 slot, L, p;
@@ -1707,27 +1707,4 @@ __device__ __forceinline__ uint32_t dense_word(const Desc& d, const DenseView& v
       w = dense_word_at(words, L * v.Wl + q, wbits);
   }
   return w;
-}
-
-// word of each key this table owns (NO_WORD for unreachable / not owned)
-__global__ void k_dense_query(Desc d, DenseView v, const uint32_t* words, const u64* bits, const u64* keys, u64 n,
-                              uint32_t* out, uint32_t wbits) {
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x)
-    out[i] = dense_word(d, v, words, bits, wbits, keys[i]);
-}
-
-// every reachable owned position -> its key (order arbitrary); v sweeps the
-// whole local range with the own-slice filter
-__global__ void k_dense_positions(Desc d, DenseView v, const u64* bits, u64 levels, u64* out, u64 cap, u64* count) {
-  const u64 n = v.Wl;
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < levels * n; i += (u64)gridDim.x * blockDim.x) {
-    const u64 L = i / n, q = i - L * n;
-    bool run;
-    const u64 p = dense_global(v, q, &run);
-    if (!run) continue;
-    int64_t h0 = dense_h0(d, L, p);
-    if (h0 < 0 || !reach_bit(bits, L * v.Wbl + q)) continue;
-    u64 k = atomicAdd(count, 1ull);
-    if (k < cap) out[k] = p * d.base[0] + (u64)h0;
-  }
 }

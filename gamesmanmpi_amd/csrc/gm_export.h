@@ -13,7 +13,7 @@
 //        PLANES   k_plane_export_bits: the one-bit-per-row map expanded
 //        RANKED   a copy of the reach words (slot order is index order)
 //        generic  k_export_generic<WF, false>: index -> key -> the layout's
-//                 "word of key" functor (gm_moves.h), one ballot per wave
+//                 "word of key" functor (gm_table.h), one ballot per wave
 //   2. k_export_counts: reached indexes per block (popcounts) and, per
 //      workgroup of 256 blocks, their sum
 //   3. k_export_scan_top / k_export_offsets: the exclusive scan over the
@@ -66,7 +66,7 @@ struct ExportIndex {
   bool toot;
   u64 total;      // sum games: positions of the rank space (index = key)
   RankGeom g;     // toot: C, H, A, T, nslots and lvph
-  const u64* lvt;  // toot: k_rk_scan's level tables
+  const u64* lvt;  // toot: RankEnum's level tables (gm_table.h)
   __device__ __forceinline__ bool key(u64 idx, u64* out) const {
     if (!toot) {
       *out = idx;

@@ -12,7 +12,8 @@
 // bucket(key) = the top bucket_bits bits of mix64(key) (0 when bucket_bits is
 // 0).  Four passes on the solver's stream, (key, word) pairs coming from a
 // pair source -- the layout's position enumerator and "word of key" functor
-// (gm_moves.h), or K[i] / W[i] side by side on BUCKETED (TkFlat):
+// (TkLookup), or BUCKETED's own pair source, K[i] / W[i] side by side
+// (FlatPairs, gm_table.h):
 //   1. k_tk_count    positions per bucket (u32): a histogram in LDS, flushed
 //                    once per workgroup for its non-empty bins, when the
 //                    2^bucket_bits counters fit gm_census.h's LDS budget
@@ -44,8 +45,8 @@ enum { TK_OR = 0, TK_BAD = 1, TK_MAXBUCKET = 2, TK_WORDS = 4 };
 __device__ __forceinline__ u64 tk_bucket(u64 key, uint32_t b) { return b ? mix64(key) >> (64u - b) : 0ull; }
 
 // ---------------------------------------------------------------------------
-// pair sources: items() work items, visit(d, i, f) calls f(key, word) for each
-// position of item i
+// the pair source (gm_table.h) that reads nothing in place: the deliberately
+// independent path GM_EXPORT_GENERIC keeps
 // ---------------------------------------------------------------------------
 template <class EN, class WF>
 struct TkLookup {  // any layout: enumerate the keys, look each word up
@@ -55,16 +56,6 @@ struct TkLookup {  // any layout: enumerate the keys, look each word up
   template <class F>
   __device__ __forceinline__ void visit(const Desc& d, u64 i, F&& f) const {
     en.visit(d, i, [&](u64 key) { f(key, wf(d, key)); });
-  }
-};
-struct TkFlat {  // BUCKETED: W[i] is the word of K[i] (bk_word reads W[L.lb + j] for K[L.lb + j])
-  const u64* K;
-  const uint32_t* W;
-  u64 n;
-  __device__ __forceinline__ u64 items() const { return n; }
-  template <class F>
-  __device__ __forceinline__ void visit(const Desc&, u64 i, F&& f) const {
-    f(K[i], W[i]);
   }
 };
 
@@ -201,9 +192,7 @@ __global__ __launch_bounds__(256) void k_tk_sort(const u64* __restrict__ dir, u6
 template <class F>
 static void tk_source_dispatch(gm_solver* s, bool generic, F&& f) {
   if (!generic && s->mode == GM_MODE_BUCKETED) {
-    u64 tot = 0;
-    for (const BkLevel& x : s->lvh) tot += x.n;
-    f(TkFlat{s->bkK, s->bkW, tot});
+    f(FlatPairs{{s->bkK, bk_positions(s)}, s->bkW});
     return;
   }
   moves_words_dispatch(s, [&](auto wf) {

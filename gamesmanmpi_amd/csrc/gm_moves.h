@@ -9,56 +9,15 @@
 //
 // One device primitive serves all three calls: expand a key with the device
 // descriptor (any_prim / any_children, gm_games.h), fetch every child's word
-// through the layout's own locate path -- the device functions the query
-// kernels are made of (hashed_word, dense_word, bk_word, plane_word<WB>,
-// rk_word), wrapped in one small "word of key" functor per layout -- and
-// reduce with the reference-canonical rule (k_resolve).  Nothing here goes
+// through the layout's "word of key" functor (gm_table.h: the locate path
+// gm_solver_query runs) and reduce with the reference-canonical rule
+// (k_resolve).  Nothing here goes
 // through the register-resident wavefronts that wrote the tables
 // (k_plane_flow, k_rk_backward, k_bk_reduce, the dense resolvers), so the
 // audit is an independent check of them.
 //
-// Included by gm_solver.hip inside its extern "C" block, after the solver
-// object and every layout header.
+// Included by gm_solver.hip inside its extern "C" block, after gm_table.h.
 extern "C++" {
-
-// ---------------------------------------------------------------------------
-// word of key, per layout
-// ---------------------------------------------------------------------------
-struct HashedWords {
-  const gm_slot* tab;
-  u64 mask;
-  __device__ __forceinline__ uint32_t operator()(const Desc& d, u64 key) const { return hashed_word(d, tab, mask, key); }
-};
-struct DenseWords {
-  DenseView v;
-  const uint32_t* words;
-  const u64* bits;
-  uint32_t wbits;
-  __device__ __forceinline__ uint32_t operator()(const Desc& d, u64 key) const {
-    return dense_word(d, v, words, bits, wbits, key);
-  }
-};
-struct BkWords {
-  const u64* K;
-  const uint32_t* W;
-  const BkLevelDev* lv;
-  int T;
-  const uint32_t* meta;
-  __device__ __forceinline__ uint32_t operator()(const Desc& d, u64 key) const { return bk_word(d, K, W, lv, T, meta, key); }
-};
-template <int WB>
-struct PlaneWords {
-  PlaneGeom g;
-  const void* tab;
-  const uint32_t* bits;
-  __device__ __forceinline__ uint32_t operator()(const Desc& d, u64 key) const {
-    return plane_word<WB>(d, g, tab, bits, key);
-  }
-};
-struct RankWords {
-  RankGeom g;
-  __device__ __forceinline__ uint32_t operator()(const Desc&, u64 key) const { return rk_word(g, key); }
-};
 
 // ---------------------------------------------------------------------------
 // the reduction (k_resolve's rule) and the best-move rule
@@ -263,76 +222,7 @@ __global__ __launch_bounds__(64) void k_line(Desc d, WF wf, u64 key, u64* __rest
 // ---------------------------------------------------------------------------
 // k_audit: every stored word against the reduction of its children's words
 // ---------------------------------------------------------------------------
-// Position enumerators, one per way a layout lists its reachable positions:
-// items() work items, visit(d, i, f) calls f(key) for each position of item i.
-struct HashedEnum {  // the level key store (HASHED)
-  const u64* lv;
-  u64 lcap;
-  const DevState* st;
-  __device__ __forceinline__ u64 items() const { return st->cursor_front + st->cursor_back; }
-  template <class F>
-  __device__ __forceinline__ void visit(const Desc&, u64 i, F&& f) const {
-    const u64 nf = st->cursor_front;
-    f(i < nf ? lv[i] : lv[lcap - 1 - (i - nf)]);
-  }
-};
-struct FlatEnum {  // every level's keys, contiguous (BUCKETED)
-  const u64* K;
-  u64 n;
-  __device__ __forceinline__ u64 items() const { return n; }
-  template <class F>
-  __device__ __forceinline__ void visit(const Desc&, u64 i, F&& f) const {
-    f(K[i]);
-  }
-};
-struct DenseEnum {  // index -> key, as k_dense_positions
-  DenseView v;
-  const u64* bits;
-  u64 levels;
-  __device__ __forceinline__ u64 items() const { return levels * v.Wl; }
-  template <class F>
-  __device__ __forceinline__ void visit(const Desc& d, u64 i, F&& f) const {
-    const u64 L = i / v.Wl, q = i - L * v.Wl;
-    bool run;
-    const u64 p = dense_global(v, q, &run);
-    if (!run) return;
-    const int64_t h0 = dense_h0(d, L, p);
-    if (h0 < 0 || !reach_bit(bits, L * v.Wbl + q)) return;
-    f(p * d.base[0] + (u64)h0);
-  }
-};
-template <int NO>
-struct PlaneEnum {  // one plane row (32 positions) per item, as k_plane_positions
-  PlaneGeom g;
-  const uint32_t* bits;
-  __device__ __forceinline__ u64 items() const { return (u64)g.nplanes * 32u; }
-  template <class F>
-  __device__ __forceinline__ void visit(const Desc& d, u64 i, F&& f) const {
-    uint32_t w = plane_row_bits(bits, g, i >> 5, (uint32_t)i & 31u);
-    if (!w) return;
-    const u64 base = plane_key<NO>(d, g, (uint32_t)(i >> 5), 0, (uint32_t)i & 31u);
-    for (; w; w &= w - 1) f(base + (u64)__builtin_ctz(w));
-  }
-};
-struct RankEnum {  // one 64-slot word of the reach bitmap per item, as k_rk_scan
-  RankGeom g;
-  const u64* lvt;
-  uint32_t T;
-  u64 nwords;
-  __device__ __forceinline__ u64 items() const { return nwords; }
-  template <class F>
-  __device__ __forceinline__ void visit(const Desc&, u64 wi, F&& f) const {
-    u64 m = reinterpret_cast<const u64*>(g.reach)[wi];
-    if (!m) return;
-    const u64* lvstart = lvt;
-    const u64* lvoff = lvt + T + 1;
-    const u64 s0 = wi << 6;
-    uint32_t L = 0;
-    while (L + 1 < T && lvstart[L + 1] <= s0) L++;
-    for (; m; m &= m - 1) f(rk_slot_key(g, lvstart, lvoff, L, s0 + (u64)__builtin_ctzll(m)));
-  }
-};
-
+// (the layout's position enumerator and "word of key" functor, gm_table.h)
 // acc[0..3]: positions, edges, mismatches, the cursor of `bad` (mismatching
 // keys appended, the first `cap` kept).  Reads the table only.
 template <class EN, class WF>
@@ -365,50 +255,8 @@ __global__ __launch_bounds__(256) void k_audit(Desc d, EN en, WF wf, u64* __rest
 }
 
 // ---------------------------------------------------------------------------
-// host: layout dispatch and the three ABI calls' bodies
+// host: the three ABI calls' bodies
 // ---------------------------------------------------------------------------
-// f(word functor) for the solver's layout
-template <class F>
-static void moves_words_dispatch(gm_solver* s, F&& f) {
-  if (s->mode == GM_MODE_PLANES)
-    plane_form_dispatch(s, [&](auto WB, auto) {
-      f(PlaneWords<decltype(WB)::value>{s->pg, (const void*)s->ptab, (const uint32_t*)s->pbits});
-    });
-  else if (s->mode == GM_MODE_RANKED)
-    f(RankWords{s->rg});
-  else if (s->mode == GM_MODE_DENSE)
-    f(DenseWords{s->view, s->words, s->bits, s->wbits()});
-  else if (s->mode == GM_MODE_BUCKETED)
-    f(BkWords{s->bkK, s->bkW, s->bkL, s->d.max_levels, s->meta});
-  else
-    f(HashedWords{s->tab, s->mask});
-}
-// f(position enumerator) for the solver's layout
-template <class F>
-static void moves_enum_dispatch(gm_solver* s, F&& f) {
-  if (s->mode == GM_MODE_PLANES)
-    plane_no_dispatch(s->pg.no, [&](auto NO) { f(PlaneEnum<decltype(NO)::value>{s->pg, (const uint32_t*)s->pbits}); });
-  else if (s->mode == GM_MODE_RANKED)
-    f(RankEnum{s->rg, (const u64*)s->rlv_dev, s->rg.T, s->rg.nslots / 64});
-  else if (s->mode == GM_MODE_DENSE)
-    f(DenseEnum{s->view, s->bits, (u64)s->d.max_levels});
-  else if (s->mode == GM_MODE_BUCKETED) {
-    u64 tot = 0;
-    for (const BkLevel& x : s->lvh) tot += x.n;
-    f(FlatEnum{s->bkK, tot});
-  } else
-    f(HashedEnum{s->lv, s->lcap, s->st});
-}
-
-// one-GPU solvers holding a finished full solve
-static int moves_ready(const gm_solver* s, const char* what) {
-  if (s->world > 1)
-    return fail(GM_EINVAL, "%s: shard %d/%d holds part of the table (its positions' children live on other ranks); "
-                           "one-GPU solvers only", what, s->rank, s->world);
-  if (!s->solved) return fail(GM_EINVAL, "%s: the solver holds no finished full solve", what);
-  return 0;
-}
-
 static int moves_run(gm_solver* s, const uint64_t* keys_dev, uint64_t n, uint64_t* children_dev, uint32_t* words_dev,
                      uint8_t* nchild_dev, int8_t* best_dev) {
   const int grid = (int)std::min<u64>((n + kBlock - 1) / kBlock, (u64)s->grid);

@@ -72,7 +72,7 @@ __device__ __forceinline__ bool plane_locate(const Desc& d, const PlaneGeom& g, 
 }
 
 // word of `key` in this table's planes (NO_WORD if unreached or not held
-// here); shared by k_plane_query and the move kernels (gm_moves.h)
+// here): PlaneWords (gm_table.h)
 template <int WB>
 __device__ __forceinline__ uint32_t plane_word(const Desc& d, const PlaneGeom& g, const void* tab,
                                                const uint32_t* bits, u64 key) {
@@ -81,13 +81,6 @@ __device__ __forceinline__ uint32_t plane_word(const Desc& d, const PlaneGeom& g
   if (plane_locate(d, g, key, &P, &h0, &h1, &e) && ((plane_row_bits(bits, g, P, h1) >> h0) & 1u))
     w = plane_vr<WB>(tab, P, h0, h1, e);
   return w;
-}
-
-template <int WB>
-__global__ void k_plane_query(Desc d, PlaneGeom g, const void* tab, const uint32_t* bits, const u64* keys, u64 n,
-                              uint32_t* out) {
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x)
-    out[i] = plane_word<WB>(d, g, tab, bits, keys[i]);
 }
 
 // the end of a solve, one launch: the root's word (only the shard that owns
@@ -193,38 +186,6 @@ __device__ __forceinline__ u64 plane_key(const Desc& d, const PlaneGeom& g, uint
   }
   if (osum) *osum = t;
   return k;
-}
-
-template <int NO>
-__global__ void k_plane_positions(Desc d, PlaneGeom g, const uint32_t* bits, u64* out, u64 cap, u64* count) {
-  const u64 nw = (u64)g.nplanes * 32u;
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < nw; i += (u64)gridDim.x * blockDim.x) {
-    uint32_t w = plane_row_bits(bits, g, i >> 5, (uint32_t)i & 31u);
-    if (!w) continue;
-    u64 k = atomicAdd(count, (u64)__builtin_popcount(w));
-    const u64 base = plane_key<NO>(d, g, (uint32_t)(i >> 5), 0, (uint32_t)i & 31u);
-    for (; w; w &= w - 1, k++)
-      if (k < cap) out[k] = base + (u64)__builtin_ctz(w);
-  }
-}
-
-template <int NO, int WB>
-__global__ __launch_bounds__(256) void k_plane_checksum(Desc d, PlaneGeom g, const void* tab, const uint32_t* bits,
-                                                        u64* acc) {
-  u64 a[6] = {0, 0, 0, 0, 0, 0};
-  const u64 nw = (u64)g.nplanes * 32u;
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < nw; i += (u64)gridDim.x * blockDim.x) {
-    const uint32_t P = (uint32_t)(i >> 5), h1 = (uint32_t)i & 31u;
-    uint32_t w = plane_row_bits(bits, g, P, h1);
-    if (!w) continue;
-    uint32_t os;
-    const u64 base = plane_key<NO>(d, g, P, 0, h1, &os);
-    for (; w; w &= w - 1) {
-      const uint32_t h0 = (uint32_t)__builtin_ctz(w);
-      ck_add(d, base + h0, plane_vr<WB>(tab, P, h0, h1, os + h0 + h1 + g.h1off), a);
-    }
-  }
-  ck_block_add(acc, a);
 }
 
 // ---------------------------------------------------------------------------
@@ -1909,42 +1870,6 @@ static int plane_collect(gm_solver* s, u64 ticket, gm_result* out) {
   out->ms_expand_kernels = out->ms_resolve_kernels = 0;
   out->n_expand_launches = out->n_resolve_launches = 0;
   return plane_result({s}, red, out);
-}
-
-static int plane_query(gm_solver* s, const uint64_t* keys_dev, uint64_t n, uint32_t* words_dev) {
-  const int grid = (int)std::min<u64>((n + kBlock - 1) / kBlock, (u64)s->grid);
-  plane_form_dispatch(s, [&](auto WB, auto) {
-    hipLaunchKernelGGL(k_plane_query<decltype(WB)::value>, dim3(grid), dim3(kBlock), 0, s->stream, s->d, s->pg,
-                       (const void*)s->ptab, s->pbits, (const u64*)keys_dev, n, words_dev);
-  });
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(s->stream));
-  return 0;
-}
-
-static int plane_positions(gm_solver* s, uint64_t* keys_dev, uint64_t cap, uint64_t* n) {
-  u64 cnt = 0;
-  HIPCHK(hipStreamSynchronize(s->stream));
-  HIPCHK(hipMemcpy(&cnt, &s->st->cursor_front, sizeof cnt, hipMemcpyDeviceToHost));
-  *n = cnt;
-  if (cnt > cap || !keys_dev) return cap < cnt ? fail(GM_EFULL, "need %llu slots", (unsigned long long)cnt) : 0;
-  HIPCHK(hipMemsetAsync(&s->st->cursor_back, 0, sizeof(u64), s->stream));
-  plane_no_dispatch(s->pg.no, [&](auto NO) {
-    hipLaunchKernelGGL((k_plane_positions<decltype(NO)::value>), dim3(s->grid), dim3(kBlock), 0, s->stream, s->d,
-                       s->pg, (const uint32_t*)s->pbits, (u64*)keys_dev, cap, &s->st->cursor_back);
-  });
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(s->stream));
-  return 0;
-}
-
-static void plane_checksum_launch(gm_solver* s, u64* acc) {
-  plane_no_dispatch(s->pg.no, [&](auto NO) {
-    plane_form_dispatch(s, [&](auto WB, auto) {
-      hipLaunchKernelGGL((k_plane_checksum<decltype(NO)::value, decltype(WB)::value>), dim3(s->grid), dim3(kBlock), 0,
-                         s->stream, s->d, s->pg, (const void*)s->ptab, (const uint32_t*)s->pbits, acc);
-    });
-  });
 }
 
 }  // extern "C++"

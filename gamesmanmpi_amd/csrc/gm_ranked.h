@@ -844,8 +844,8 @@ __global__ __launch_bounds__(1024) void k_rk_finish(RankGeom g, u64 root_slot, D
   fill_red_body(st, bc);
 }
 
-// word of `key` at its computed slot (NO_WORD if unreached); shared by
-// k_rk_query and the move kernels (gm_moves.h)
+// word of `key` at its computed slot (NO_WORD if unreached): RankWords
+// (gm_table.h)
 __device__ __forceinline__ uint32_t rk_word(const RankGeom& g, u64 key) {
   u64 s;
   uint32_t L, w = NO_WORD;
@@ -853,12 +853,7 @@ __device__ __forceinline__ uint32_t rk_word(const RankGeom& g, u64 key) {
   return w;
 }
 
-__global__ void k_rk_query(Desc d, RankGeom g, const u64* keys, u64 n, uint32_t* out) {
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x)
-    out[i] = rk_word(g, keys[i]);
-}
-
-// key of reached slot s0 + bit of level L (lvstart / lvoff: k_rk_scan's lvt halves)
+// key of reached slot s0 + bit of level L (lvstart / lvoff: the halves of RankEnum's lvt, gm_table.h)
 __device__ __forceinline__ u64 rk_slot_key(const RankGeom& g, const u64* lvstart, const u64* lvoff, uint32_t L,
                                            u64 slot) {
   const u64 i = slot - lvstart[L];
@@ -867,33 +862,6 @@ __device__ __forceinline__ u64 rk_slot_key(const RankGeom& g, const u64* lvstart
   RankPos p;
   rk_unpack(g, g.lvph[lvoff[L] + blk], p);
   return rk_key(g, p, pat, L, rk_hands(L, (uint32_t)__builtin_popcount(pat), a));
-}
-
-// every reached slot of every level: its key (positions) or its fingerprint
-// term (checksum); one thread per 64-slot word of the reach bitmap
-// (lvt: the levels' first slots [0, T], then their first block entries [T + 1, 2T + 1])
-template <bool CK>
-__global__ __launch_bounds__(256) void k_rk_scan(Desc d, RankGeom g, const u64* lvt, uint32_t T, u64 nwords, u64* keys,
-                                                 u64 cap, u64* count, u64* acc) {
-  const u64* lvstart = lvt;
-  const u64* lvoff = lvt + T + 1;
-  u64 v[6] = {0, 0, 0, 0, 0, 0};
-  for (u64 wi = (u64)blockIdx.x * blockDim.x + threadIdx.x; wi < nwords; wi += (u64)gridDim.x * blockDim.x) {
-    u64 m = reinterpret_cast<const u64*>(g.reach)[wi];
-    if (!m) continue;
-    const u64 s0 = wi << 6;
-    uint32_t L = 0;
-    while (L + 1 < T && lvstart[L + 1] <= s0) L++;
-    u64 k = 0;
-    if (!CK) k = atomicAdd(count, (u64)__builtin_popcountll(m));
-    for (; m; m &= m - 1, k++) {
-      const u64 slot = s0 + (u64)__builtin_ctzll(m);
-      const u64 key = rk_slot_key(g, lvstart, lvoff, L, slot);
-      if (CK) ck_add(d, key, g.words[slot], v);
-      else if (k < cap) keys[k] = key;
-    }
-  }
-  if (CK) ck_block_add(acc, v);
 }
 
 // ---------------------------------------------------------------------------
@@ -1053,7 +1021,7 @@ static int rank_setup(gm_solver* s, const gm_buffers* buf) {
   s->rlvoff = rs.lvoff;
   s->rlvstart = rs.lvstart;
   s->rlvitems = rs.lvitems;
-  // the per-level tables the scans read on the device (k_rk_scan's lvt)
+  // the per-level tables the scans read on the device (RankEnum's lvt)
   if (!s->rlv_dev) HIPCHK(hipMalloc((void**)&s->rlv_dev, (size_t)(2 * (rs.g.T + 1)) * 8));
   std::vector<u64> tabs(2 * (rs.g.T + 1), 0);
   for (uint32_t L = 0; L <= rs.g.T; L++) {
@@ -1237,39 +1205,6 @@ static int run_ranked(gm_solver* s, gm_result* out) {
   out->root_value = (int32_t)(word & 3u);
   out->root_remoteness = word >> 2;
   return 0;
-}
-
-static int rank_query(gm_solver* s, const uint64_t* keys_dev, uint64_t n, uint32_t* words_dev) {
-  const int grid = (int)std::min<u64>((n + kBlock - 1) / kBlock, (u64)s->grid);
-  hipLaunchKernelGGL(k_rk_query, dim3(grid), dim3(kBlock), 0, s->stream, s->d, s->rg, (const u64*)keys_dev, n,
-                     words_dev);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(s->stream));
-  return 0;
-}
-
-static int rank_scan(gm_solver* s, bool ck, u64* keys_dev, u64 cap, u64* acc) {
-  const RankGeom& g = s->rg;
-  const u64 nwords = g.nslots / 64;
-  if (ck)
-    hipLaunchKernelGGL((k_rk_scan<true>), dim3(s->grid), dim3(256), 0, s->stream, s->d, g, (const u64*)s->rlv_dev, g.T,
-                       nwords, (u64*)nullptr, (u64)0, (u64*)nullptr, acc);
-  else
-    hipLaunchKernelGGL((k_rk_scan<false>), dim3(s->grid), dim3(256), 0, s->stream, s->d, g, (const u64*)s->rlv_dev, g.T,
-                       nwords, keys_dev, cap, &s->st->cursor_back, (u64*)nullptr);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(s->stream));
-  return 0;
-}
-
-static int rank_positions(gm_solver* s, uint64_t* keys_dev, uint64_t cap, uint64_t* n) {
-  u64 cnt = 0;
-  HIPCHK(hipStreamSynchronize(s->stream));
-  HIPCHK(hipMemcpy(&cnt, &s->st->cursor_front, sizeof cnt, hipMemcpyDeviceToHost));
-  *n = cnt;
-  if (cnt > cap || !keys_dev) return cap < cnt ? fail(GM_EFULL, "need %llu slots", (unsigned long long)cnt) : 0;
-  HIPCHK(hipMemsetAsync(&s->st->cursor_back, 0, sizeof(u64), s->stream));
-  return rank_scan(s, false, (u64*)keys_dev, cap, nullptr);
 }
 
 }  // extern "C++"

@@ -11,8 +11,8 @@
 //   gm_dense.h           DENSE kernels
 //   gm_keyed_shard.h     md5-sharded HASHED kernels (gm_ks_*)
 //   gm_bucketed.h        BUCKETED kernels
-//   (here)               checksum kernels, struct gm_solver, the HASHED host
-//                        path (run_hashed), the codec C-ABI, k_fill_red
+//   (here)               struct gm_solver, the HASHED host path (run_hashed),
+//                        the codec C-ABI, k_fill_red
 //   gm_xchg.h            the shards' exchange layer: transport modes and group
 //                        checks, all-gather, ranged send / receive, the
 //                        end-of-solve reduction (no kernels)
@@ -23,6 +23,8 @@
 //   gm_bucketed_run.h    BUCKETED host path (no kernels)
 //   gm_bucketed_shard.h  md5-sharded BUCKETED levels
 //   (here)               the C-ABI over the layouts: plans, creation, solves
+//   gm_table.h           the layout views (word of key, position enumerator,
+//                        pair source); query, positions, checksum
 //   gm_moves.h           move analysis and the table audit
 //   gm_census.h          the census by value, remoteness and level
 //   (here)               readers, gm_solve, gm_ks_*, the explicit-graph solve
@@ -900,16 +902,10 @@ __global__ __launch_bounds__(256) void k_resolve(Desc d, gm_slot* tab, u64 mask,
   block_add(&st->prims, prims);
 }
 
-// word of `key` in the hash table (NO_WORD if absent); shared by k_query and
-// the move kernels (gm_moves.h)
+// word of `key` in the hash table (NO_WORD if absent): HashedWords (gm_table.h)
 __device__ __forceinline__ uint32_t hashed_word(const Desc& d, const gm_slot* tab, u64 mask, u64 key) {
   u64 h = table_find(tab, mask, any_canon(d, key));  // symmetry hooks: the orbit's representative
   return h == ~0ull ? NO_WORD : tab[h].word;
-}
-
-__global__ void k_query(Desc d, const gm_slot* tab, u64 mask, const u64* keys, u64 n, uint32_t* words) {
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x)
-    words[i] = hashed_word(d, tab, mask, keys[i]);
 }
 
 __global__ void k_root_word(const gm_slot* tab, u64 mask, u64 root, DevState* st) {
@@ -917,12 +913,6 @@ __global__ void k_root_word(const gm_slot* tab, u64 mask, u64 root, DevState* st
     u64 h = table_find(tab, mask, root);
     st->root_word = h == ~0ull ? NO_WORD : tab[h].word;
   }
-}
-
-__global__ void k_gather_positions(const u64* lv, u64 lcap, const DevState* st, u64* out) {
-  u64 nf = st->cursor_front, nb = st->cursor_back;
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < nf + nb; i += (u64)gridDim.x * blockDim.x)
-    out[i] = i < nf ? lv[i] : lv[lcap - 1 - (i - nf)];
 }
 
 
@@ -936,66 +926,6 @@ __global__ void k_owner(Desc d, const u64* keys, u64 n, uint32_t P, uint32_t* ow
     owners[i] = owner_dev(d, keys[i], P);
 }
 #include "gm_bucketed.h"
-
-// ---------------------------------------------------------------------------
-// whole-solve fingerprint (gm_solver_checksum): per block partial sums of
-// pos_checksum and the value histogram, one atomic per block and field
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ void ck_block_add(u64* acc, u64 (&v)[6]) {
-  __shared__ u64 part[16][6];
-#pragma unroll
-  for (int f = 0; f < 6; f++)
-    for (int o = 32; o > 0; o >>= 1) v[f] += __shfl_xor(v[f], o);
-  const int w = threadIdx.x >> 6;
-  if (__lane_id() == 0)
-    for (int f = 0; f < 6; f++) part[w][f] = v[f];
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    u64 t = 0;
-    for (int i = 0; i < (int)(blockDim.x >> 6); i++) t += part[i][threadIdx.x];
-    if (t) atomicAdd(&acc[threadIdx.x], t);
-  }
-}
-__device__ __forceinline__ void ck_add(const Desc& d, u64 key, uint32_t word, u64 (&v)[6]) {
-  uint8_t c[40];
-  const int n = canon_from_key(d, key, c);
-  v[0] += pos_checksum(c, n, word & 3u, word >> 2);
-  v[1] += 1;
-  v[2 + (word & 3u)] += 1;
-}
-__global__ __launch_bounds__(256) void k_checksum_hashed(Desc d, const gm_slot* tab, u64 mask, const u64* lv, u64 lcap,
-                                                         const DevState* st, u64* acc) {
-  u64 v[6] = {0, 0, 0, 0, 0, 0};
-  const u64 nf = st->cursor_front, nb = st->cursor_back;
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < nf + nb; i += (u64)gridDim.x * blockDim.x) {
-    const u64 key = i < nf ? lv[i] : lv[lcap - 1 - (i - nf)];
-    const u64 h = table_find(tab, mask, key);
-    ck_add(d, key, h == ~0ull ? NO_WORD : tab[h].word, v);
-  }
-  ck_block_add(acc, v);
-}
-__global__ __launch_bounds__(256) void k_checksum_flat(Desc d, const u64* K, const uint32_t* W, u64 n, u64* acc) {
-  u64 v[6] = {0, 0, 0, 0, 0, 0};
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x)
-    ck_add(d, K[i], W[i], v);
-  ck_block_add(acc, v);
-}
-__global__ __launch_bounds__(256) void k_checksum_dense(Desc d, DenseView v, const uint32_t* words, const u64* bits,
-                                                        u64 levels, uint32_t wbits, u64* acc) {
-  u64 a[6] = {0, 0, 0, 0, 0, 0};
-  const u64 n = v.Wl;
-  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < levels * n; i += (u64)gridDim.x * blockDim.x) {
-    const u64 L = i / n, q = i - L * n;
-    bool run;
-    const u64 p = dense_global(v, q, &run);
-    if (!run) continue;
-    const int64_t h0 = dense_h0(d, L, p);
-    if (h0 < 0 || !reach_bit(bits, L * v.Wbl + q)) continue;
-    const uint32_t w = dense_word_at(words, L * v.Wl + q, wbits);
-    ck_add(d, p * d.base[0] + (u64)h0, w, a);
-  }
-  ck_block_add(acc, a);
-}
 
 // ---------------------------------------------------------------------------
 // solver object
@@ -1177,7 +1107,7 @@ struct gm_solver {
   RankGeom rg{};
   std::vector<uint32_t> rlvoff;        // per level: first entry of its block list
   std::vector<u64> rlvstart, rlvitems;  // per level: first slot, slots
-  u64* rlv_dev = nullptr;              // device: rlvstart then rlvoff (k_rk_scan)
+  u64* rlv_dev = nullptr;              // device: rlvstart then rlvoff (RankEnum's lvt)
   u64* cen_dev = nullptr;              // device: gm_solver_census' counts, maxima and witnesses (gm_census.h)
   // gm_solver_export (gm_export.h): block offsets and totals of a call (device,
   // grown on demand); for toot tables of the keyed layouts the level tables
@@ -2045,7 +1975,7 @@ int gm_solve_group(gm_solver** shards, int n, gm_result* out) {
   return rc;
 }
 
-
+#include "gm_table.h"
 #include "gm_moves.h"
 
 int gm_solver_moves(gm_solver* s, const uint64_t* keys_dev, uint64_t n, uint64_t* children_dev, uint32_t* words_dev,
@@ -2159,81 +2089,17 @@ int gm_solver_export_keyed(gm_solver* s, uint32_t how, uint32_t bucket_bits, uin
 int gm_solver_query(gm_solver* s, const uint64_t* keys_dev, uint64_t n, uint32_t* words_dev) {
   if (!s || (n && (!keys_dev || !words_dev))) return fail(GM_EINVAL, "bad argument");
   if (!n) return 0;
-  if (s->mode == GM_MODE_PLANES) return plane_query(s, keys_dev, n, words_dev);
-  if (s->mode == GM_MODE_RANKED) return rank_query(s, keys_dev, n, words_dev);
-  int grid = (int)std::min<u64>((n + kBlock - 1) / kBlock, (u64)s->grid);
-  if (s->mode == GM_MODE_DENSE)
-    hipLaunchKernelGGL(k_dense_query, dim3(grid), dim3(kBlock), 0, s->stream, s->d, s->view, s->words, s->bits,
-                       (const u64*)keys_dev, n, words_dev, s->wbits());
-  else if (s->mode == GM_MODE_BUCKETED)
-    hipLaunchKernelGGL(k_bk_query, dim3(grid), dim3(kBlock), 0, s->stream, s->d, s->bkK, s->bkW, s->bkL,
-                       s->d.max_levels, s->meta, (const u64*)keys_dev, n, words_dev);
-  else
-    hipLaunchKernelGGL(k_query, dim3(grid), dim3(kBlock), 0, s->stream, s->d, s->tab, s->mask, (const u64*)keys_dev, n,
-                       words_dev);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(s->stream));
-  return 0;
+  return query_run(s, keys_dev, n, words_dev);
 }
 
 int gm_solver_positions(gm_solver* s, uint64_t* keys_dev, uint64_t cap, uint64_t* n) {
   if (!s || !n) return fail(GM_EINVAL, "bad argument");
-  if (s->mode == GM_MODE_PLANES) return plane_positions(s, keys_dev, cap, n);
-  if (s->mode == GM_MODE_RANKED) return rank_positions(s, keys_dev, cap, n);
-  if (s->mode == GM_MODE_BUCKETED) {  // every level's keys, contiguous
-    u64 tot = 0;
-    for (const BkLevel& x : s->lvh) tot += x.n;
-    *n = tot;
-    if (tot > cap || !keys_dev) return cap < tot ? fail(GM_EFULL, "need %llu slots", (unsigned long long)tot) : 0;
-    HIPCHK(hipMemcpyAsync(keys_dev, s->bkK, tot * sizeof(u64), hipMemcpyDeviceToDevice, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return 0;
-  }
-  u64 cur[2];
-  HIPCHK(hipStreamSynchronize(s->stream));
-  HIPCHK(hipMemcpy(cur, s->st, sizeof cur, hipMemcpyDeviceToHost));
-  *n = s->mode == GM_MODE_DENSE ? cur[0] : cur[0] + cur[1];
-  if (s->mode == GM_MODE_DENSE) {
-    if (*n > cap || !keys_dev) return cap < *n ? fail(GM_EFULL, "need %llu slots", (unsigned long long)*n) : 0;
-    HIPCHK(hipMemsetAsync(&s->st->cursor_back, 0, sizeof(u64), s->stream));
-    hipLaunchKernelGGL(k_dense_positions, dim3(s->grid), dim3(kBlock), 0, s->stream, s->d, s->view, s->bits,
-                       (u64)s->d.max_levels, (u64*)keys_dev, cap, &s->st->cursor_back);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return 0;
-  }
-  if (*n > cap || !keys_dev) return cap < *n ? fail(GM_EFULL, "need %llu slots", (unsigned long long)*n) : 0;
-  hipLaunchKernelGGL(k_gather_positions, dim3(s->grid), dim3(kBlock), 0, s->stream, s->lv, s->lcap, s->st,
-                     (u64*)keys_dev);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(s->stream));
-  return 0;
+  return positions_run(s, keys_dev, cap, n);
 }
 
 int gm_solver_checksum(gm_solver* s, uint64_t out[6]) {
   if (!s || !out) return fail(GM_EINVAL, "bad argument");
-  u64* acc = s->st->ck;
-  HIPCHK(hipMemsetAsync(acc, 0, 6 * sizeof(u64), s->stream));
-  if (s->mode == GM_MODE_PLANES)
-    plane_checksum_launch(s, acc);
-  else if (s->mode == GM_MODE_RANKED) {
-    int rc = rank_scan(s, true, nullptr, 0, acc);
-    if (rc) return rc;
-  }
-  else if (s->mode == GM_MODE_DENSE)
-    hipLaunchKernelGGL(k_checksum_dense, dim3(s->grid), dim3(kBlock), 0, s->stream, s->d, s->view, s->words, s->bits,
-                       (u64)s->d.max_levels, s->wbits(), acc);
-  else if (s->mode == GM_MODE_BUCKETED) {
-    u64 tot = 0;
-    for (const BkLevel& x : s->lvh) tot += x.n;
-    hipLaunchKernelGGL(k_checksum_flat, dim3(s->grid), dim3(kBlock), 0, s->stream, s->d, s->bkK, s->bkW, tot, acc);
-  } else
-    hipLaunchKernelGGL(k_checksum_hashed, dim3(s->grid), dim3(kBlock), 0, s->stream, s->d, s->tab, s->mask, s->lv,
-                       s->lcap, s->st, acc);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, acc, 6 * sizeof(u64), hipMemcpyDeviceToHost, s->stream));
-  HIPCHK(hipStreamSynchronize(s->stream));
-  return 0;
+  return checksum_run(s, out);
 }
 
 // gm_solve keeps its solver per game id until the next gm_solve of that game

@@ -163,7 +163,7 @@ def test_gpu_one_shot_solve_and_query(name, golden_summary):
     """SURVEY §8b's one-shot pair: gm_solve(game, root, 1, buffers) then
     gm_query(game, keys, n, words) on the table it keeps, every golden
     position's word bit-exact (toot 4x3 and tic-tac-toe on BUCKETED levels:
-    the home-slot search of k_bk_query); gm_release drops it and a query then
+    the home-slot search of bk_word); gm_release drops it and a query then
     fails."""
     import ctypes
     import torch
