@@ -121,7 +121,7 @@ class gm_result(ctypes.Structure):
 # every symbol include/gamesman.h declares (tests check the exports)
 EXPORTS = (
     "gm_game_lookup", "gm_game_info", "gm_root", "gm_encode", "gm_decode",
-    "gm_encode_batch", "gm_decode_batch", "gm_str_utf8", "gm_host_expand", "gm_host_level", "gm_symmetry", "gm_symmetry_count", "gm_abi_sizes", "gm_plan", "gm_solver_create",
+    "gm_encode_batch", "gm_decode_batch", "gm_str_utf8", "gm_host_expand", "gm_host_expand_fixed", "gm_host_level", "gm_symmetry", "gm_symmetry_count", "gm_abi_sizes", "gm_plan", "gm_solver_create",
     "gm_solver_solve", "gm_solver_solve_async", "gm_solver_collect", "gm_solver_query", "gm_solver_positions",
     "gm_solver_checksum", "gm_solver_moves", "gm_solver_line", "gm_solver_audit", "gm_solver_census",
     "gm_solver_destroy", "gm_solve", "gm_plan_multi", "gm_query", "gm_release", "gm_owner", "gm_owner_host",
@@ -167,6 +167,8 @@ def load():
                         P(c.c_size_t)],
         "gm_host_expand": [c.c_int, c.c_void_p, c.c_size_t, c.c_void_p,
                            c.c_void_p, c.c_void_p],
+        "gm_host_expand_fixed": [c.c_int, c.c_void_p, c.c_size_t, c.c_void_p,
+                                 c.c_void_p, c.c_void_p],
         "gm_host_level": [c.c_int, c.c_void_p, c.c_size_t, c.c_void_p],
         "gm_symmetry": [c.c_int, c.c_int, c.c_void_p, c.c_size_t, c.c_void_p],
         "gm_symmetry_count": [c.c_int, P(c.c_uint32)],

@@ -12,7 +12,7 @@ extern "C++" {
 // of pieces placed): the bucketed pipeline applies (gm_bucketed.h)
 // every move advances one level, and remoteness < 256 (packed backward answers)
 static bool bk_ok(const Desc* d) {
-  return (d->kind == K_TTT || d->kind == K_TOOT || d->kind == K_OTHELLO) && d->max_levels <= 256;
+  return (d->kind == K_TTT || d->kind == K_TOOT || d->kind == K_OTHELLO || d->kind == K_CONNECT) && d->max_levels <= 256;
 }
 // edges bound for a positions bound: the known counts where the board and
 // bound match (SURVEY Appendix B / tests/golden), else a branching factor
@@ -26,7 +26,10 @@ static const BkKnown* bk_known(const Desc* d) {
       {K_TOOT, 3, 3, 11097ull, 27774ull},          {K_TOOT, 4, 3, 200127ull, 640648ull},
       {K_TOOT, 4, 4, 3468773ull, 9932808ull},      {K_TOOT, 5, 4, 70184763ull, 226547754ull},
       {K_TOOT, 6, 4, 1187212827ull, 4243234712ull}, {K_OTHELLO, 4, 4, 54089ull, 69916ull},
-      {K_TTT, 0, 0, 5478ull, 16167ull}};
+      {K_TTT, 0, 0, 5478ull, 16167ull},
+      // connect four, connect 4 (tests/golden/connect_four/summary.json)
+      {K_CONNECT, 4, 4, 161029ull, 304574ull},     {K_CONNECT, 5, 4, 3945711ull, 8757625ull}};
+  if (d->kind == K_CONNECT && d->variant != 4) return nullptr;
   for (const BkKnown& k : kn)
     if (k.kind == d->kind && (d->kind == K_TTT || (k.L == d->L && k.H == d->H))) return &k;
   return nullptr;
@@ -34,7 +37,8 @@ static const BkKnown* bk_known(const Desc* d) {
 static u64 bk_edges_bound(const Desc* d, u64 P) {
   const BkKnown* k = bk_known(d);
   if (k && P <= k->P) return k->E + 1024;
-  const double ratio = d->kind == K_TOOT ? 3.6 : d->kind == K_TTT ? 3.0 : 2.0;
+  // (connect four: at most one move per column)
+  const double ratio = d->kind == K_TOOT ? 3.6 : d->kind == K_TTT ? 3.0 : d->kind == K_CONNECT ? (double)d->L : 2.0;
   return (u64)(ratio * (double)P) + 1024;
 }
 // out-edges of the P positions an md5 shard owns: the md5 partition spreads
@@ -117,6 +121,9 @@ static void bk_dispatch_plain(const Desc& d, Fn&& fn) {
     case K_TOOT_5x4: fn(std::integral_constant<int, K_TOOT_5x4>{}); break;
     case K_TOOT_4x4: fn(std::integral_constant<int, K_TOOT_4x4>{}); break;
     case K_TOOT: fn(std::integral_constant<int, K_TOOT>{}); break;
+    case K_CONNECT_5x4: fn(std::integral_constant<int, K_CONNECT_5x4>{}); break;
+    case K_CONNECT_6x5: fn(std::integral_constant<int, K_CONNECT_6x5>{}); break;
+    case K_CONNECT: fn(std::integral_constant<int, K_CONNECT>{}); break;
     default: fn(std::integral_constant<int, K_OTHELLO>{}); break;
   }
 }

@@ -8,6 +8,7 @@
 //   toot_and_otto_bitstring       : latin-1 bytes of the MSB-first bitstring
 //                                   (board_to_bytes, toot_and_otto_bitstring.py:229-236)
 //   othello_bit_new               : same (othello_bit_new.py:241-248)
+//   connect_four                  : the L*H-char string of "-XO" (games/connect_four.py)
 // __host__ __device__ so the owner kernel can render str(pos) on device.
 #pragma once
 #include "gm_games.h"
@@ -78,9 +79,28 @@ GM_HD int key_from_bits(const Desc& d, const uint8_t* b, int n, uint64_t* key) {
   return 0;
 }
 
+// connect four: key <-> the A characters of str(pos), cell i at byte i
+GM_HD int connect_chars_from_key(const Desc& d, uint64_t k, uint8_t* out) {
+  for (int i = 0; i < d.A; i++)
+    out[i] = ((k >> i) & 1) ? (uint8_t)'X' : ((k >> (d.A + i)) & 1) ? (uint8_t)'O' : (uint8_t)'-';
+  return d.A;
+}
+GM_HD int connect_key_from_chars(const Desc& d, const uint8_t* b, int n, uint64_t* key) {
+  if (n != d.A) return -1;
+  uint64_t k = 0;
+  for (int i = 0; i < d.A; i++) {
+    if (b[i] == 'X') k |= 1ull << i;
+    else if (b[i] == 'O') k |= 1ull << (d.A + i);
+    else if (b[i] != '-') return -1;
+  }
+  *key = k;
+  return 0;
+}
+
 // key -> canonical bytes; returns the length
 GM_HD int canon_from_key(const Desc& d, uint64_t k, uint8_t* out) {
   if (d.kind == K_TOOT || d.kind == K_OTHELLO) return bits_from_key(d, k, out);
+  if (d.kind == K_CONNECT) return connect_chars_from_key(d, k, out);
   if (d.kind == K_TTT) {
     for (int c = 0; c < 9; c++) {
       uint32_t v = (uint32_t)((k >> (2 * c)) & 3);
@@ -106,7 +126,7 @@ GM_HD int str_utf8_from_key(const Desc& d, uint64_t k, uint8_t* out) {
     }
     return n;
   }
-  if (d.kind == K_TTT && d.variant == 1) return canon_from_key(d, k, out);
+  if (d.kind == K_CONNECT || (d.kind == K_TTT && d.variant == 1)) return canon_from_key(d, k, out);
   if (d.kind == K_TTT) {  // numpy str() of a 3x3 int8 array
     int n = 0;
     for (int r = 0; r < 3; r++) {

@@ -38,7 +38,8 @@ enum GameKind : int {
   K_SUM = 1,     // four_to_one.py (1 heap) and sum_four_to_one.py (K heaps)
   K_TTT = 2,     // tic_tac_toe_np.py and mttt.py (same graph)
   K_TOOT = 3,    // toot_and_otto_bitstring.py
-  K_OTHELLO = 4  // othello_bit_new.py (square boards)
+  K_OTHELLO = 4, // othello_bit_new.py (square boards)
+  K_CONNECT = 5  // games/connect_four.py (L x H, connect K)
 };
 
 constexpr int MAXCHILD = 32;
@@ -52,7 +53,8 @@ GM_HD uint32_t make_word(int value, uint32_t rem) { return (uint32_t)value | (re
 // ---------------------------------------------------------------------------
 struct Desc {
   int kind;
-  int variant;     // K_TTT: 0 = tic_tac_toe_np, 1 = mttt; K_SUM: 0 = sum, 1 = four_to_one
+  int variant;     // K_TTT: 0 = tic_tac_toe_np, 1 = mttt; K_SUM: 0 = sum, 1 = four_to_one;
+                   // K_CONNECT: K, the pieces in a row that win
   int L, H, A;     // board games
   int nbits;       // bitstring length (toot/othello canonical form)
   // K_SUM
@@ -63,11 +65,12 @@ struct Desc {
   uint32_t shift[16];
   uint64_t stride[16];
   uint32_t root_sum;
-  // K_TOOT word-start masks (directions (1,0),(0,1),(1,1),(1,-1))
+  // K_TOOT word-start masks (directions (1,0),(0,1),(1,1),(1,-1));
+  // K_CONNECT: the start cells of the K-cell lines, same directions and steps
   uint64_t tmask[4];
   int tstep[4];
   uint64_t full;   // all-cells mask
-  uint64_t col0;   // K_TOOT: the cells of column 0 (bit L*y for every y)
+  uint64_t col0;   // K_TOOT, K_CONNECT: the cells of column 0 (bit L*y for every y)
   uint64_t root;   // root key
   int max_levels;  // levels the pipeline must provision (root level = 0)
   // K_SUM dense (perfect-hash) layout: slot = level * W + prefix, where
@@ -83,7 +86,7 @@ struct Desc {
   // symmetry_functions() (othello_bit_new.py:224-226: player_flip, order 2)
   int sym;
   // board symmetry (params "board_symmetry=1"; gm_sym.h): keys are the
-  // smallest image under the game's board group.  K_TOOT: the mirror's
+  // smallest image under the game's board group.  K_TOOT, K_CONNECT: the mirror's
   // delta-swap masks, swap i exchanging bit i and bit L-1-i of every row
   int bsym;
   int nmir;
@@ -483,6 +486,131 @@ GM_HD int oth_level(const Desc& d, uint64_t k) {
 }
 
 // ---------------------------------------------------------------------------
+// Connect Four (gamesmanmpi_amd/games/connect_four.py), L x H, K in a row
+// (Desc::variant).  key bits: [0,A) X plane, [A,2A) O plane, cell index
+// L*y+x with y = 0 the bottom row: the toot planes without hands or turn bit.
+// Level = pieces on the board; X moves at even levels.
+// ---------------------------------------------------------------------------
+// cells of plane p that start a line of n of its pieces along step s, under
+// the start-cell mask m (which forbids a line that would wrap a row)
+GM_HD uint64_t connect_run(uint64_t p, uint64_t m, int s, int n) {
+  if (n == 4) {  // the two-step form
+    const uint64_t t = p & shr_s(p, s);
+    return m & t & shr_s(t, 2 * s);
+  }
+  for (int j = 1; j < n; j++) m &= shr_s(p, j * s);
+  return m & p;
+}
+GM_HD bool connect_line(const Desc& d, uint64_t p) {
+  uint64_t any = 0;
+  for (int i = 0; i < 4; i++) any |= connect_run(p, d.tmask[i], d.tstep[i], d.variant);
+  return any != 0;
+}
+GM_HD int connect_prim(const Desc& d, uint64_t k) {
+  const uint64_t x = k & d.full, o = (k >> d.A) & d.full;
+  if (connect_line(d, x) || connect_line(d, o)) return LOSS;  // checked before fullness
+  return ((x | o) == d.full) ? TIE : UNDECIDED;
+}
+template <class F>
+GM_HD int connect_children(const Desc& d, uint64_t k, F&& emit) {
+  const int A = d.A, L = d.L, H = d.H;
+  const uint64_t occ = (k | (k >> A)) & d.full;
+  const int plane = (popc64(occ) & 1) ? A : 0;  // X moves when the piece count is even
+  int n = 0;
+  for (int x = 0; x < L; x++) {
+    if ((occ >> (L * (H - 1) + x)) & 1) continue;  // column full
+    const uint64_t blank = ~(occ >> x) & d.col0;  // lowest blank cell, as toot_children
+    const uint64_t cell = (blank & (~blank + 1)) << x;
+    emit(k | (cell << plane), 1);
+    n++;
+  }
+  return n;
+}
+template <class F>
+GM_HD int connect_children_sym(const Desc& d, uint64_t k, F&& emit) {
+  return connect_children(d, k, [&](uint64_t c, int step) { emit(sym_toot_canon(d, c), step); });
+}
+GM_HD int connect_level(const Desc&, uint64_t k) { return popc64(k); }
+
+// The same rules with board and line length fixed at compile time, as
+// TootFixed: bit-identical to connect_prim / connect_children (tests: both
+// forms agree on playouts and solve to the same words).
+template <int L, int H, int K>
+struct ConnectFixed {
+  static constexpr int A = L * H;
+  static constexpr uint64_t full = (1ull << A) - 1;
+  static constexpr uint64_t col0() {
+    uint64_t m = 0;
+    for (int y = 0; y < H; y++) m |= 1ull << (L * y);
+    return m;
+  }
+  static constexpr uint64_t lmask(int i) {
+    const int dxs[4] = {1, 0, 1, 1}, dys[4] = {0, 1, 1, -1};
+    uint64_t m = 0;
+    for (int x = 0; x < L; x++)
+      for (int y = 0; y < H; y++) {
+        const int ex = x + (K - 1) * dxs[i], ey = y + (K - 1) * dys[i];
+        if (ex >= 0 && ex < L && ey >= 0 && ey < H) m |= 1ull << (L * y + x);
+      }
+    return m;
+  }
+  static constexpr int lstep(int i) {
+    const int dxs[4] = {1, 0, 1, 1}, dys[4] = {0, 1, 1, -1};
+    return dxs[i] + L * dys[i];
+  }
+  template <int S>
+  static GM_HD uint64_t shr(uint64_t v) {
+    if constexpr (S >= 0) return v >> S;
+    else return v << (-S);
+  }
+  template <int S, int J>
+  static GM_HD uint64_t and_from(uint64_t p, uint64_t m) {
+    if constexpr (J < K) return and_from<S, J + 1>(p, m & shr<J * S>(p));
+    else return m;
+  }
+  template <int I>
+  static GM_HD uint64_t run(uint64_t p) {
+    constexpr int s = lstep(I);
+    constexpr uint64_t m = lmask(I);
+    if constexpr (m == 0) {
+      return 0;
+    } else if constexpr (K == 4) {
+      const uint64_t t = p & shr<s>(p);
+      return m & t & shr<2 * s>(t);
+    } else {
+      return and_from<s, 0>(p, m);
+    }
+  }
+  static GM_HD bool line(uint64_t p) { return (run<0>(p) | run<1>(p) | run<2>(p) | run<3>(p)) != 0; }
+  static GM_HD int prim(const Desc&, uint64_t k) {
+    const uint64_t x = k & full, o = (k >> A) & full;
+    if (line(x) || line(o)) return LOSS;
+    return ((x | o) == full) ? TIE : UNDECIDED;
+  }
+  template <class F>
+  static GM_HD int children(const Desc&, uint64_t k, F&& emit) {
+    const uint64_t occ = (k | (k >> A)) & full;
+    const int plane = (popc64(occ) & 1) ? A : 0;
+    int n = 0;
+#pragma unroll
+    for (int x = 0; x < L; x++) {
+      if ((occ >> (L * (H - 1) + x)) & 1) continue;  // column full
+      const uint64_t blank = ~(occ >> x) & col0();
+      const uint64_t cell = (blank & (~blank + 1)) << x;
+      emit(k | (cell << plane), 1);
+      n++;
+    }
+    return n;
+  }
+  static GM_HD uint64_t mirror(uint64_t k) { return sym_toot_mirror_fixed<L, H>(k); }
+  template <class F>
+  static GM_HD int children_sym(const Desc& d, uint64_t k, F&& emit) {
+    return children(d, k, [&](uint64_t c, int step) { emit(sym_min(c, mirror(c)), step); });
+  }
+  static GM_HD int level(const Desc&, uint64_t k) { return popc64(k); }
+};
+
+// ---------------------------------------------------------------------------
 // Static dispatch.  children(d, key, emit) calls emit(child, level_step) in
 // gen_moves() order and returns the child count.
 // ---------------------------------------------------------------------------
@@ -507,9 +635,20 @@ constexpr int K_TOOT_6x4 = 64, K_TOOT_5x4 = 54, K_TOOT_4x4 = 44;
 template <> struct Game<K_TOOT_6x4> : TootFixed<6, 4> { static constexpr bool kFixed = true; };
 template <> struct Game<K_TOOT_5x4> : TootFixed<5, 4> { static constexpr bool kFixed = true; };
 template <> struct Game<K_TOOT_4x4> : TootFixed<4, 4> { static constexpr bool kFixed = true; };
-// the instantiation id for a descriptor: a fixed toot board where one exists
+template <> struct Game<K_CONNECT> {
+  static GM_HD int prim(const Desc& d, uint64_t k) { return connect_prim(d, k); }
+  template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return connect_children(d, k, f); }
+  static GM_HD int level(const Desc& d, uint64_t k) { return connect_level(d, k); }
+};
+// compile-time connect-four boards, connect 4
+constexpr int K_CONNECT_5x4 = 154, K_CONNECT_6x5 = 165;
+template <> struct Game<K_CONNECT_5x4> : ConnectFixed<5, 4, 4> { static constexpr bool kFixed = true; };
+template <> struct Game<K_CONNECT_6x5> : ConnectFixed<6, 5, 4> { static constexpr bool kFixed = true; };
+// the instantiation id for a descriptor: a fixed board where one exists
 GM_HD int fixed_kind(const Desc& d) {
   if (d.kind == K_TOOT && d.H == 4 && d.L >= 4 && d.L <= 6) return d.L * 10 + 4;
+  if (d.kind == K_CONNECT && d.variant == 4 && d.L == 5 && d.H == 4) return K_CONNECT_5x4;
+  if (d.kind == K_CONNECT && d.variant == 4 && d.L == 6 && d.H == 5) return K_CONNECT_6x5;
   return d.kind;
 }
 template <> struct Game<K_OTHELLO> {
@@ -541,6 +680,19 @@ template <> struct Game<K_TOOT_4x4 | K_SYM> : Game<K_TOOT_4x4> {
 template <> struct Game<K_OTHELLO | K_SYM> : Game<K_OTHELLO> {
   template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return oth_children_sym(d, k, f); }
 };
+template <> struct Game<K_CONNECT | K_SYM> : Game<K_CONNECT> {
+  template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return connect_children_sym(d, k, f); }
+};
+template <> struct Game<K_CONNECT_5x4 | K_SYM> : Game<K_CONNECT_5x4> {
+  template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return children_sym(d, k, f); }
+};
+template <> struct Game<K_CONNECT_6x5 | K_SYM> : Game<K_CONNECT_6x5> {
+  template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return children_sym(d, k, f); }
+};
+// an instantiation id of connect four (generic or fixed, plain or symmetric)
+constexpr bool kind_is_connect(int kind) {
+  return kind_base(kind) == K_CONNECT || kind_base(kind) == K_CONNECT_5x4 || kind_base(kind) == K_CONNECT_6x5;
+}
 // the instantiation id with the symmetric form where the descriptor asks
 GM_HD int sym_kind(const Desc& d, int kind) { return d.bsym ? (kind | K_SYM) : kind; }
 
@@ -549,6 +701,7 @@ GM_HD int any_prim(const Desc& d, uint64_t k) {
     case K_SUM: return sum_prim(d, k);
     case K_TTT: return ttt_prim(d, k);
     case K_TOOT: return toot_prim(d, k);
+    case K_CONNECT: return connect_prim(d, k);
     default: return oth_prim(d, k);
   }
 }
@@ -557,12 +710,14 @@ GM_HD int any_children(const Desc& d, uint64_t k, F&& f) {
   if (d.bsym) switch (d.kind) {
     case K_TTT: return ttt_children_sym(d, k, f);
     case K_TOOT: return toot_children_sym(d, k, f);
+    case K_CONNECT: return connect_children_sym(d, k, f);
     default: return oth_children_sym(d, k, f);
   }
   switch (d.kind) {
     case K_SUM: return sum_children(d, k, f);
     case K_TTT: return ttt_children(d, k, f);
     case K_TOOT: return toot_children(d, k, f);
+    case K_CONNECT: return connect_children(d, k, f);
     default: return oth_children(d, k, f);
   }
 }
@@ -576,6 +731,7 @@ GM_HD int any_level(const Desc& d, uint64_t k) {
     case K_SUM: return sum_level(d, k);
     case K_TTT: return ttt_level(d, k);
     case K_TOOT: return toot_level(d, k);
+    case K_CONNECT: return connect_level(d, k);
     default: return oth_level(d, k);
   }
 }

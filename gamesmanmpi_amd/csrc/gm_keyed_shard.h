@@ -159,9 +159,32 @@ __device__ __forceinline__ uint32_t owner_fast_g(const OwnerGeom d, u64 k, uint3
   M[14] = len * 8u;
   return md5_mod_words(M, P);
 }
+// connect four: str(pos) is the A <= 30 characters of "-XO", cell i at byte
+// i -- static byte positions, one block.  A function of its own (not a
+// branch of owner_fast_g), so that the other kinds' kernels keep their code.
+__device__ __forceinline__ uint32_t owner_connect(int A, u64 k, uint32_t P) {
+  if (P <= 1) return 0;
+  uint32_t M[16];
+#pragma unroll
+  for (int w = 0; w < 16; w++) M[w] = 0;
+  const uint32_t x = (uint32_t)k & ((1u << A) - 1u), o = (uint32_t)(k >> A);
+#pragma unroll
+  for (int i = 0; i < 30; i++) {
+    const uint32_t ch = ((x >> i) & 1u) ? (uint32_t)'X' : ((o >> i) & 1u) ? (uint32_t)'O' : (uint32_t)'-';
+    M[i >> 2] |= i < A ? ch << (8 * (i & 3)) : 0u;  // (A is wave-uniform)
+  }
+#pragma unroll
+  for (int w = 0; w < 8; w++)  // the padding byte after the last character
+    if (w == (A >> 2)) M[w] |= 0x80u << (8 * (A & 3));
+  M[14] = (uint32_t)A * 8u;
+  return md5_mod_words(M, P);
+}
+__device__ __noinline__ uint32_t owner_connect_call(int A, u64 key, uint32_t P) { return owner_connect(A, key, P); }
+
 // the owner rule on the device: the register-resident form where it applies
 __device__ __forceinline__ uint32_t owner_dev(const Desc& d, u64 key, uint32_t P) {
   if (d.kind == K_TTT || d.kind == K_TOOT || d.kind == K_OTHELLO) return owner_fast(d, key, P);
+  if (d.kind == K_CONNECT) return owner_connect(d.A, key, P);
   return owner_of(d, key, P);
 }
 
@@ -172,7 +195,9 @@ __device__ __forceinline__ uint32_t owner_dev(const Desc& d, u64 key, uint32_t P
 // occupancy)
 template <int KIND>
 __device__ __forceinline__ uint32_t owner_k(const Desc& d, u64 key, uint32_t P) {
-  if constexpr (kind_base(KIND) != K_SUM)  // the board games, plain or symmetric
+  if constexpr (kind_is_connect(KIND))
+    return owner_connect(d.A, key, P);
+  else if constexpr (kind_base(KIND) != K_SUM)  // the board games, plain or symmetric
     return owner_fast(d, key, P);
   else
     return owner_dev(d, key, P);
@@ -186,7 +211,9 @@ __device__ __noinline__ uint32_t owner_fast_call(const OwnerGeom d, u64 key, uin
 // as a call, for a kernel specialised to KIND (no scratch-array path for the fast kinds)
 template <int KIND>
 __device__ __forceinline__ uint32_t owner_call_k(const Desc& d, u64 key, uint32_t P) {
-  if constexpr (kind_base(KIND) != K_SUM)  // the board games, plain or symmetric
+  if constexpr (kind_is_connect(KIND))
+    return owner_connect_call(d.A, key, P);
+  else if constexpr (kind_base(KIND) != K_SUM)  // the board games, plain or symmetric
     return owner_fast_call(OwnerGeom{d.kind, d.variant, d.A, d.nbits}, key, P);
   else
     return owner_of_call(d, key, P);

@@ -326,6 +326,35 @@ static int build_desc(const char* name, const char* params, Desc* out) {
     d.max_levels = d.A + 3;
     d.sym = kv(params, "symmetry", 0) ? 1 : 0;  // player_flip orbits (symmetry_functions, :224-226)
     d.root = oth_canon(d, d.root);
+  } else if (!strcmp(name, "connect_four")) {
+    d.kind = K_CONNECT;
+    d.L = kv(params, "length", 5);  // games/connect_four.py
+    d.H = kv(params, "height", 4);
+    d.variant = kv(params, "connect", 4);
+    if (d.L < 1 || d.H < 1 || d.L > 8 || (long)d.L * d.H > 30)
+      return fail(GM_EINVAL, "connect four board %dx%d: at most 8 columns and 30 cells fit the key "
+                             "(two planes of L*H bits; 7x6 is out of reach)", d.L, d.H);
+    d.A = d.L * d.H;
+    if (d.variant < 1 || d.variant > (d.L > d.H ? d.L : d.H))
+      return fail(GM_EINVAL, "connect=%d: a line on a %dx%d board has 1..%d cells", d.variant, d.L, d.H,
+                  d.L > d.H ? d.L : d.H);
+    d.full = (1ull << d.A) - 1;
+    for (int y = 0; y < d.H; y++) d.col0 |= 1ull << (d.L * y);
+    // line starts per direction: (1,0) (0,1) (1,1) (1,-1); a start cell's
+    // whole line is on the board, so no shifted copy wraps a row
+    const int dxs[4] = {1, 0, 1, 1}, dys[4] = {0, 1, 1, -1};
+    for (int i = 0; i < 4; i++) {
+      uint64_t m = 0;
+      for (int x = 0; x < d.L; x++)
+        for (int y = 0; y < d.H; y++) {
+          int ex = x + (d.variant - 1) * dxs[i], ey = y + (d.variant - 1) * dys[i];
+          if (ex >= 0 && ex < d.L && ey >= 0 && ey < d.H) m |= 1ull << (d.L * y + x);
+        }
+      d.tmask[i] = m;
+      d.tstep[i] = dxs[i] + d.L * dys[i];
+    }
+    d.root = 0;
+    d.max_levels = d.A + 1;
   } else {
     return fail(GM_EINVAL, "no device descriptor for game '%s'", name);
   }
@@ -333,13 +362,13 @@ static int build_desc(const char* name, const char* params, Desc* out) {
     return fail(GM_EINVAL, "'%s' defines no symmetry_functions() to reduce by", name);
   if (kv(params, "board_symmetry", 0)) {  // orbit representatives under the board's group (gm_sym.h)
     if (d.kind == K_SUM)
-      return fail(GM_EINVAL, "'%s' has no board: board_symmetry=1 covers tic-tac-toe, toot-and-otto and othello "
+      return fail(GM_EINVAL, "'%s' has no board: board_symmetry=1 covers tic-tac-toe, toot-and-otto, othello and connect four "
                              "(heap permutations are not implemented)", name);
     if (kv(params, "symmetry", 0))
       return fail(GM_EINVAL, "board_symmetry=1 and symmetry=1 do not combine: player_flip swaps the colours "
                              "the board maps keep");
     d.bsym = 1;
-    if (d.kind == K_TOOT) {
+    if (d.kind == K_TOOT || d.kind == K_CONNECT) {  // the same two planes of H rows
       d.nmir = d.L / 2;
       for (int i = 0; i < d.nmir; i++) d.mir[i] = sym_toot_mask(d.L, d.H, i);
     }
@@ -1155,12 +1184,14 @@ static void do_expand(gm_solver* s, int L) {
   if (s->d.bsym) switch (s->d.kind) {  // children as orbit representatives (gm_sym.h)
     case K_TTT: return enqueue_level_expand<K_TTT | K_SYM>(s, L);
     case K_TOOT: return enqueue_level_expand<K_TOOT | K_SYM>(s, L);
+    case K_CONNECT: return enqueue_level_expand<K_CONNECT | K_SYM>(s, L);
     default: return enqueue_level_expand<K_OTHELLO | K_SYM>(s, L);
   }
   switch (s->d.kind) {
     case K_SUM: enqueue_level_expand<K_SUM>(s, L); break;
     case K_TTT: enqueue_level_expand<K_TTT>(s, L); break;
     case K_TOOT: enqueue_level_expand<K_TOOT>(s, L); break;
+    case K_CONNECT: enqueue_level_expand<K_CONNECT>(s, L); break;
     default: enqueue_level_expand<K_OTHELLO>(s, L); break;
   }
 }
@@ -1168,12 +1199,14 @@ static void do_resolve(gm_solver* s, int L) {
   if (s->d.bsym) switch (s->d.kind) {
     case K_TTT: return enqueue_level_resolve<K_TTT | K_SYM>(s, L);
     case K_TOOT: return enqueue_level_resolve<K_TOOT | K_SYM>(s, L);
+    case K_CONNECT: return enqueue_level_resolve<K_CONNECT | K_SYM>(s, L);
     default: return enqueue_level_resolve<K_OTHELLO | K_SYM>(s, L);
   }
   switch (s->d.kind) {
     case K_SUM: enqueue_level_resolve<K_SUM>(s, L); break;
     case K_TTT: enqueue_level_resolve<K_TTT>(s, L); break;
     case K_TOOT: enqueue_level_resolve<K_TOOT>(s, L); break;
+    case K_CONNECT: enqueue_level_resolve<K_CONNECT>(s, L); break;
     default: enqueue_level_resolve<K_OTHELLO>(s, L); break;
   }
 }
@@ -1306,6 +1339,27 @@ int gm_game_lookup(const char* name, const char* params, int* game_id) {
   return 0;
 }
 
+// boards of L columns of 0..H pieces with n pieces in all, times the ways to
+// colour them with ceil(n/2) X and floor(n/2) O, summed over n (L*H <= 30:
+// every term fits 64 bits)
+static uint64_t connect_fillings(int L, int H) {
+  const int A = L * H;
+  uint64_t ways[31] = {1}, choose[31][31] = {};
+  for (int c = 0; c < L; c++) {  // one column more: heights 0..H
+    uint64_t next[31] = {};
+    for (int n = 0; n <= A; n++)
+      for (int h = 0; h <= H && n + h <= A; h++) next[n + h] += ways[n];
+    memcpy(ways, next, sizeof ways);
+  }
+  for (int n = 0; n <= A; n++) {
+    choose[n][0] = 1;
+    for (int r = 1; r <= n; r++) choose[n][r] = choose[n - 1][r - 1] + (r <= n - 1 ? choose[n - 1][r] : 0);
+  }
+  uint64_t total = 0;
+  for (int n = 0; n <= A; n++) total += ways[n] * choose[n][n / 2];
+  return total;
+}
+
 int gm_game_info(int game, uint64_t* positions_bound, uint32_t* max_levels, uint32_t* key_bits) {
   const Desc* d = get_game(game);
   if (!d) return fail(GM_EINVAL, "bad game id %d", game);
@@ -1332,6 +1386,14 @@ int gm_game_info(int game, uint64_t* positions_bound, uint32_t* max_levels, uint
       bits = 2 * d->A + 13;
       break;
     }
+    case K_CONNECT:
+      // the enumerated (and published) counts where known, else the gravity
+      // fillings with balanced colours, wins ignored: a true upper bound
+      if (d->L == 4 && d->H == 4 && d->variant == 4) bound = 161029;
+      else if (d->L == 5 && d->H == 4 && d->variant == 4) bound = 3945711;
+      else bound = connect_fillings(d->L, d->H);
+      bits = 2 * d->A;
+      break;
     default:
       if (d->L == 4) bound = 54089;
       else bound = 0;
@@ -1355,6 +1417,11 @@ int gm_encode(int game, const uint8_t* canon, size_t n, uint64_t* key) {
   if (!d || !canon || !key) return fail(GM_EINVAL, "bad argument");
   if (d->kind == K_TOOT || d->kind == K_OTHELLO) {
     if (key_from_bits(*d, canon, (int)n, key)) return fail(GM_EINVAL, "bytes are not a %s position", d->kind == K_TOOT ? "toot" : "othello");
+    return 0;
+  }
+  if (d->kind == K_CONNECT) {
+    if (connect_key_from_chars(*d, canon, (int)n, key))
+      return fail(GM_EINVAL, "connect four positions are %d characters of - X O", d->A);
     return 0;
   }
   if (d->kind == K_TTT) {
@@ -2017,6 +2084,32 @@ int gm_solver_census(gm_solver* s, uint32_t how, uint64_t* by_rem_dev, uint32_t 
 
 #include "gm_export.h"
 
+// gm_host_expand through the instantiation the bucketed kernels run for this
+// descriptor (fixed_kind: a compile-time board where one exists, symmetric
+// where the descriptor asks), so that both forms can be compared on the host
+int gm_host_expand_fixed(int game, const uint64_t* keys, size_t n, uint64_t* children, uint8_t* nchild, uint8_t* prim) {
+  const Desc* d = get_game(game);
+  if (!d || (n && (!keys || !children || !nchild || !prim))) return fail(GM_EINVAL, "bad argument");
+  if (!bk_ok(d)) return fail(GM_EINVAL, "the game has no bucketed kernels");
+  bool over = false;
+  bk_dispatch(*d, [&](auto kind_) {
+    constexpr int K_ = decltype(kind_)::value;
+    for (size_t i = 0; i < n; i++) {
+      prim[i] = (uint8_t)Game<K_>::prim(*d, keys[i]);
+      int c = 0;
+      if (prim[i] == UNDECIDED)
+        Game<K_>::children(*d, keys[i], [&](uint64_t ck, int) {
+          if (c < GM_MAXCHILD) children[i * GM_MAXCHILD + c] = ck;
+          c++;
+        });
+      over |= c > GM_MAXCHILD;
+      nchild[i] = (uint8_t)c;
+    }
+  });
+  if (over) return fail(GM_ECORRUPT, "more than %d children", GM_MAXCHILD);
+  return 0;
+}
+
 int gm_tb_info(int game, uint64_t* index_space) {
   const Desc* d = get_game(game);
   if (!d || !index_space) return fail(GM_EINVAL, "bad argument");
@@ -2357,9 +2450,11 @@ int gm_owner(int game, const uint64_t* keys_dev, uint64_t n, int world_size, uin
     GM_KIND_CASE(KERNEL, K_TTT, GRID, S, __VA_ARGS__)                 \
     GM_KIND_CASE(KERNEL, K_TOOT, GRID, S, __VA_ARGS__)                \
     GM_KIND_CASE(KERNEL, K_OTHELLO, GRID, S, __VA_ARGS__)             \
+    GM_KIND_CASE(KERNEL, K_CONNECT, GRID, S, __VA_ARGS__)             \
     GM_KIND_CASE(KERNEL, K_TTT | K_SYM, GRID, S, __VA_ARGS__)         \
     GM_KIND_CASE(KERNEL, K_TOOT | K_SYM, GRID, S, __VA_ARGS__)        \
     GM_KIND_CASE(KERNEL, K_OTHELLO | K_SYM, GRID, S, __VA_ARGS__)     \
+    GM_KIND_CASE(KERNEL, K_CONNECT | K_SYM, GRID, S, __VA_ARGS__)     \
   }
 // kernels that never generate children (k_ks_insert, k_ks_reduce)
 #define GM_KIND_DISPATCH_PLAIN(KERNEL, GRID, S, ...)                  \
@@ -2368,6 +2463,7 @@ int gm_owner(int game, const uint64_t* keys_dev, uint64_t n, int world_size, uin
     GM_KIND_CASE(KERNEL, K_TTT, GRID, S, __VA_ARGS__)                 \
     GM_KIND_CASE(KERNEL, K_TOOT, GRID, S, __VA_ARGS__)                \
     GM_KIND_CASE(KERNEL, K_OTHELLO, GRID, S, __VA_ARGS__)             \
+    GM_KIND_CASE(KERNEL, K_CONNECT, GRID, S, __VA_ARGS__)             \
   }
 
 static int ks_check(gm_solver* s, int level) {

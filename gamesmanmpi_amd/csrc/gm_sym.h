@@ -20,6 +20,8 @@
 //     planes, floor(L/2) delta swaps whose masks cover the 2H rows of the
 //     T and O planes at once (constexpr in TootFixed<L,H>::mirror, Desc::mir
 //     for the generic form)
+//   connect four (any board): 0 the same mirror of its X and O planes, with
+//     the same masks (ConnectFixed<L,H,K>::mirror, Desc::mir)
 //   othello LxL, the maps that keep the colours of the start position:
 //     0 the 180-degree turn (bit reversal of each A-bit plane)
 //     1 the transpose       2 the anti-transpose (turn of the transpose)
@@ -130,17 +132,17 @@ GM_HD uint64_t sym_oth_canon(const Desc& d, uint64_t k) {
 // ---- any game -------------------------------------------------------------
 // maps of the descriptor's board group (identity excluded); 0: no group here
 GM_HD int sym_board_maps(const Desc& d) {
-  return d.kind == K_TTT ? kSymTttMaps : d.kind == K_TOOT ? 1 : d.kind == K_OTHELLO ? kSymOthMaps : 0;
+  return d.kind == K_TTT ? kSymTttMaps : (d.kind == K_TOOT || d.kind == K_CONNECT) ? 1 : d.kind == K_OTHELLO ? kSymOthMaps : 0;
 }
 GM_HD uint64_t sym_board_map(const Desc& d, uint64_t k, int which) {
   if (d.kind == K_TTT) return sym_ttt_map(k, which);
-  if (d.kind == K_TOOT) return sym_toot_mirror(d, k);
+  if (d.kind == K_TOOT || d.kind == K_CONNECT) return sym_toot_mirror(d, k);
   return sym_oth_map(d, k, which);
 }
 // the orbit's representative: the smallest image
 GM_HD uint64_t sym_board_canon(const Desc& d, uint64_t k) {
   if (d.kind == K_TTT) return sym_ttt_canon(k);
-  if (d.kind == K_TOOT) return sym_toot_canon(d, k);
+  if (d.kind == K_TOOT || d.kind == K_CONNECT) return sym_toot_canon(d, k);
   return sym_oth_canon(d, k);
 }
 

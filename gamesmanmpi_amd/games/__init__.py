@@ -20,7 +20,8 @@ from .. import _lib
 # file stem -> how the module's positions map to canonical bytes
 _INT_GAMES = ("four_to_one", "sum_four_to_one")
 _BITSTRING_GAMES = ("toot_and_otto_bitstring", "othello_bit_new")
-KNOWN = _INT_GAMES + _BITSTRING_GAMES + ("tic_tac_toe_np", "mttt")
+_STRING_GAMES = ("mttt", "connect_four")  # str(pos) is the position itself
+KNOWN = _INT_GAMES + _BITSTRING_GAMES + ("tic_tac_toe_np",) + _STRING_GAMES
 
 
 class GameSpec:
@@ -125,7 +126,7 @@ class GameSpec:
             return str(int(pos)).encode("ascii")
         if self.name == "tic_tac_toe_np":
             return np.asarray(pos, dtype=np.int8).tobytes()
-        if self.name == "mttt":
+        if self.name in _STRING_GAMES:
             return pos.encode("ascii")
         return pos.encode("ISO-8859-1")
 
@@ -134,7 +135,7 @@ class GameSpec:
             return int(canon)
         if self.name == "tic_tac_toe_np":
             return np.frombuffer(canon, dtype=np.int8).reshape(3, 3).copy()
-        if self.name == "mttt":
+        if self.name in _STRING_GAMES:
             return canon.decode("ascii")
         return canon.decode("ISO-8859-1")
 
@@ -283,6 +284,9 @@ def spec_for_module(module, stem=None):
     elif stem in _BITSTRING_GAMES:
         params = "length=%d,height=%d" % (int(module.length),
                                           int(module.height))
+    elif stem == "connect_four":
+        params = "length=%d,height=%d,connect=%d" % (
+            int(module.length), int(module.height), int(module.connect))
     elif stem in ("tic_tac_toe_np", "mttt"):
         params = ""
     else:

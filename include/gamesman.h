@@ -197,8 +197,10 @@ int gm_abi_sizes(uint32_t out[3]);
 
 /* Game lookup: name = reference game-file stem ("four_to_one",
  * "sum_four_to_one", "tic_tac_toe_np", "mttt", "toot_and_otto_bitstring",
- * "othello_bit_new"); params "length=6,height=4" / "start=20" /
- * "heaps=31:31:31".  Replaces solver_launcher.py:41-42,55-66 (load +
+ * "othello_bit_new", and our own "connect_four"); params "length=6,height=4"
+ * / "start=20" / "heaps=31:31:31" / "length=5,height=4,connect=4" (connect
+ * four: at most 30 cells and 8 columns, 1 <= connect <= max(length, height),
+ * else GM_EINVAL).  Replaces solver_launcher.py:41-42,55-66 (load +
  * validate the game module). */
 int gm_game_lookup(const char *name, const char *params, int *game_id);
 
@@ -234,6 +236,12 @@ int gm_str_utf8(int game, uint64_t key, uint8_t *out, size_t cap,
 #define GM_MAXCHILD 32
 int gm_host_expand(int game, const uint64_t *keys, size_t n,
                    uint64_t *children, uint8_t *nchild, uint8_t *prim);
+/* the same through the form the BUCKETED kernels are instantiated with for
+ * this game (a compile-time board where one exists: toot-and-otto 4x4, 5x4,
+ * 6x4; connect four 5x4 and 6x5, connect 4), for checking it against the
+ * generic descriptor; GM_EINVAL for games without bucketed levels */
+int gm_host_expand_fixed(int game, const uint64_t *keys, size_t n,
+                         uint64_t *children, uint8_t *nchild, uint8_t *prim);
 /* host run of the descriptor's level function (tier of each key: the
  * number of moves from the root, counting a two-tier step as two) */
 int gm_host_level(int game, const uint64_t *keys, size_t n, int32_t *levels);
