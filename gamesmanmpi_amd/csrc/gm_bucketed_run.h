@@ -11,34 +11,18 @@ extern "C++" {
 // keyed games whose every move advances one level (the tier is the number
 // of pieces placed): the bucketed pipeline applies (gm_bucketed.h)
 // every move advances one level, and remoteness < 256 (packed backward answers)
-static bool bk_ok(const Desc* d) {
-  return (d->kind == K_TTT || d->kind == K_TOOT || d->kind == K_OTHELLO || d->kind == K_CONNECT) && d->max_levels <= 256;
-}
+static bool bk_ok(const Desc* d) { return kind_facts(d->kind).bucketed && d->max_levels <= 256; }
 // edges bound for a positions bound: the known counts where the board and
-// bound match (SURVEY Appendix B / tests/golden), else a branching factor
-// above every known board's
-struct BkKnown {
-  int kind, L, H;
-  u64 P, E;
-};
-static const BkKnown* bk_known(const Desc* d) {
-  static const BkKnown kn[] = {
-      {K_TOOT, 3, 3, 11097ull, 27774ull},          {K_TOOT, 4, 3, 200127ull, 640648ull},
-      {K_TOOT, 4, 4, 3468773ull, 9932808ull},      {K_TOOT, 5, 4, 70184763ull, 226547754ull},
-      {K_TOOT, 6, 4, 1187212827ull, 4243234712ull}, {K_OTHELLO, 4, 4, 54089ull, 69916ull},
-      {K_TTT, 0, 0, 5478ull, 16167ull},
-      // connect four, connect 4 (tests/golden/connect_four/summary.json)
-      {K_CONNECT, 4, 4, 161029ull, 304574ull},     {K_CONNECT, 5, 4, 3945711ull, 8757625ull}};
-  if (d->kind == K_CONNECT && d->variant != 4) return nullptr;
-  for (const BkKnown& k : kn)
-    if (k.kind == d->kind && (d->kind == K_TTT || (k.L == d->L && k.H == d->H))) return &k;
-  return nullptr;
+// bound match (known_board, gm_registry.h), else a branching factor above
+// every known board's
+static const KnownBoard* bk_known(const Desc* d) {
+  const KnownBoard* k = known_board(d);
+  return k && k->edges ? k : nullptr;
 }
 static u64 bk_edges_bound(const Desc* d, u64 P) {
-  const BkKnown* k = bk_known(d);
-  if (k && P <= k->P) return k->E + 1024;
-  // (connect four: at most one move per column)
-  const double ratio = d->kind == K_TOOT ? 3.6 : d->kind == K_TTT ? 3.0 : d->kind == K_CONNECT ? (double)d->L : 2.0;
+  const KnownBoard* k = bk_known(d);
+  if (k && P <= k->positions) return k->edges + 1024;
+  const double r = kind_facts(d->kind).edge_ratio, ratio = r ? r : (double)d->L;  // (0: at most one move per column)
   return (u64)(ratio * (double)P) + 1024;
 }
 // out-edges of the P positions an md5 shard owns: the md5 partition spreads
@@ -47,8 +31,9 @@ static u64 bk_edges_bound(const Desc* d, u64 P) {
 // ratio (+2 %), else the per-kind ratio; not the whole board's edges, which
 // sized every shard of toot 6x4 for the full 4.2e9 (4 shards: out of memory)
 static u64 bk_shard_edges_bound(const Desc* d, u64 P) {
-  const BkKnown* k = bk_known(d);
-  if (k && P < k->P) return std::min<u64>(k->E, (u64)((double)k->E / (double)k->P * (double)P * 1.02)) + 1024;
+  const KnownBoard* k = bk_known(d);
+  if (k && P < k->positions)
+    return std::min<u64>(k->edges, (u64)((double)k->edges / (double)k->positions * (double)P * 1.02)) + 1024;
   return bk_edges_bound(d, P);
 }
 // in-edges of the widest level: a quarter of all edges (every known board
@@ -115,24 +100,11 @@ static bool bk_ranges(u64 n, uint32_t* pshift, uint32_t* fb) {
 // bk_dispatch_plain: the symmetric kinds differ in `children` alone)
 template <class Fn>
 static void bk_dispatch_plain(const Desc& d, Fn&& fn) {
-  switch (fixed_kind(d)) {
-    case K_TTT: fn(std::integral_constant<int, K_TTT>{}); break;
-    case K_TOOT_6x4: fn(std::integral_constant<int, K_TOOT_6x4>{}); break;
-    case K_TOOT_5x4: fn(std::integral_constant<int, K_TOOT_5x4>{}); break;
-    case K_TOOT_4x4: fn(std::integral_constant<int, K_TOOT_4x4>{}); break;
-    case K_TOOT: fn(std::integral_constant<int, K_TOOT>{}); break;
-    case K_CONNECT_5x4: fn(std::integral_constant<int, K_CONNECT_5x4>{}); break;
-    case K_CONNECT_6x5: fn(std::integral_constant<int, K_CONNECT_6x5>{}); break;
-    case K_CONNECT: fn(std::integral_constant<int, K_CONNECT>{}); break;
-    default: fn(std::integral_constant<int, K_OTHELLO>{}); break;
-  }
+  kind_dispatch<BucketedKinds>(fixed_kind(d), fn);
 }
 template <class Fn>
-static void bk_dispatch(const Desc& d, Fn&& fn) {
-  if (!d.bsym) return bk_dispatch_plain(d, fn);
-  bk_dispatch_plain(d, [&](auto kind_) {  // children as orbit representatives (gm_sym.h)
-    fn(std::integral_constant<int, decltype(kind_)::value | K_SYM>{});
-  });
+static void bk_dispatch(const Desc& d, Fn&& fn) {  // children as orbit representatives where asked (gm_sym.h)
+  kind_dispatch_sym<BucketedKinds>(d, fixed_kind(d), fn);
 }
 #define BK_KIND_LAUNCH(KERNEL, GRID, BLOCK, S, ...)                                                      \
   bk_dispatch((S)->d, [&](auto kind_) {                                                                  \

@@ -12,6 +12,7 @@
 // __host__ __device__ so the owner kernel can render str(pos) on device.
 #pragma once
 #include "gm_games.h"
+#include <stdio.h>
 
 namespace gm {
 
@@ -113,6 +114,53 @@ GM_HD int canon_from_key(const Desc& d, uint64_t k, uint8_t* out) {
   do { tmp[m++] = (char)('0' + k % 10); k /= 10; } while (k);
   while (m) out[n++] = (uint8_t)tmp[--m];
   return n;
+}
+
+// canonical bytes -> key (host); returns 0, or -1 with the reason for the
+// refusal in why[]
+inline int key_from_canon(const Desc& d, const uint8_t* canon, size_t n, uint64_t* key, char (&why)[96]) {
+  auto no = [&](const char* fmt, auto... a) {
+    snprintf(why, sizeof why, fmt, a...);
+    return -1;
+  };
+  if (d.kind == K_TOOT || d.kind == K_OTHELLO) {
+    if (key_from_bits(d, canon, (int)n, key)) return no("bytes are not a %s position", d.kind == K_TOOT ? "toot" : "othello");
+    return 0;
+  }
+  if (d.kind == K_CONNECT) {
+    if (connect_key_from_chars(d, canon, (int)n, key)) return no("connect four positions are %d characters of - X O", d.A);
+    return 0;
+  }
+  if (d.kind == K_TTT) {
+    if (n != 9) return no("%s", "tic-tac-toe positions are 9 bytes");
+    uint64_t k = 0;
+    for (int c = 0; c < 9; c++) {
+      uint32_t v;
+      if (d.variant == 1) {
+        if (canon[c] == '_') v = 0;
+        else if (canon[c] == 'X') v = 1;
+        else if (canon[c] == 'O') v = 2;
+        else return no("%s", "mttt cell must be _ X or O");
+      } else {
+        if (canon[c] > 2) return no("%s", "tic_tac_toe_np cell must be 0, 1 or 2");
+        v = canon[c];
+      }
+      k |= (uint64_t)v << (2 * c);
+    }
+    *key = k;
+    return 0;
+  }
+  if (n == 0 || n > 20) return no("%s", "bad integer position");
+  unsigned __int128 v = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (canon[i] < '0' || canon[i] > '9') return no("%s", "integer positions are non-negative decimals");
+    v = v * 10 + (canon[i] - '0');
+  }
+  unsigned __int128 space = 1;
+  for (int i = 0; i < d.nheaps; i++) space *= d.base[i];
+  if (v >= space) return no("%s", "position outside the game's state space");
+  *key = (uint64_t)v;
+  return 0;
 }
 
 // str(pos).encode('utf-8'); returns the length (<= 55)

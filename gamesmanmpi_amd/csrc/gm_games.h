@@ -19,6 +19,7 @@
 //   parts").
 #pragma once
 #include <stdint.h>
+#include <type_traits>
 
 #ifndef __HIP_DEVICE_COMPILE__
 #include <string.h>
@@ -41,6 +42,10 @@ enum GameKind : int {
   K_OTHELLO = 4, // othello_bit_new.py (square boards)
   K_CONNECT = 5  // games/connect_four.py (L x H, connect K)
 };
+
+// the MD5 owner form of a kind's str(pos) (gm_keyed_shard.h): owner_of,
+// owner_fast or owner_connect
+enum OwnerRule : int { OWNER_GENERIC, OWNER_FAST, OWNER_CONNECT };
 
 constexpr int MAXCHILD = 32;
 constexpr uint64_t EMPTY_KEY = ~0ull;
@@ -327,6 +332,7 @@ GM_HD int toot_level(const Desc& d, uint64_t k) {
 // fingerprints).
 template <int L, int H>
 struct TootFixed {
+  static constexpr int kOwner = OWNER_FAST, kMaps = 1;  // (the mirror)
   static constexpr int A = L * H;
   static constexpr uint64_t full = (1ull << A) - 1;
   static constexpr uint64_t col0() {
@@ -537,6 +543,7 @@ GM_HD int connect_level(const Desc&, uint64_t k) { return popc64(k); }
 // forms agree on playouts and solve to the same words).
 template <int L, int H, int K>
 struct ConnectFixed {
+  static constexpr int kOwner = OWNER_CONNECT, kMaps = 1;  // (the mirror)
   static constexpr int A = L * H;
   static constexpr uint64_t full = (1ull << A) - 1;
   static constexpr uint64_t col0() {
@@ -612,38 +619,79 @@ struct ConnectFixed {
 
 // ---------------------------------------------------------------------------
 // Static dispatch.  children(d, key, emit) calls emit(child, level_step) in
-// gen_moves() order and returns the child count.
+// gen_moves() order and returns the child count; children_sym (the board
+// games) emits the children as orbit representatives (board_symmetry=1).
+// Beside the rules a Game<K> carries what the layers above ask about a kind:
+//   kOwner  the MD5 owner form of its str(pos) (gm_keyed_shard.h)
+//   kMaps   maps of its board group, identity excluded; 0: no board
+//   kFacts  (descriptor kinds) the host's per-kind numbers
 // ---------------------------------------------------------------------------
-template <int KIND> struct Game;
+struct KindFacts {
+  int key_extra;      // key bits beside the two planes of A cells
+  double edge_ratio;  // bucketed edge bound per position of an unknown board; 0: L (a move per column)
+  bool bucketed;      // every move advances one level: BUCKETED serves the kind
+};
+
+// the kinds of a board-symmetric descriptor (Desc::bsym): the same rules,
+// children emitted as orbit representatives.  Instantiations of their own,
+// so that a solve without the parameter runs the kernels it always ran.
+constexpr int K_SYM = 256;
+// The primary template is that symmetric adaptor: every plain id below is a
+// specialisation, and only ids with K_SYM set reach this one.
+template <int KIND> struct Game : Game<KIND & ~K_SYM> {
+  static_assert((KIND & K_SYM) != 0, "no Game<> for this kind id");
+  template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) {
+    return Game<KIND & ~K_SYM>::children_sym(d, k, f);
+  }
+};
 template <> struct Game<K_SUM> {
+  static constexpr int kOwner = OWNER_GENERIC, kMaps = 0;
+  static constexpr KindFacts kFacts = {0, 2.0, false};  // (key bits: those of the state space, gm_game_info)
   static GM_HD int prim(const Desc& d, uint64_t k) { return sum_prim(d, k); }
   template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return sum_children(d, k, f); }
   static GM_HD int level(const Desc& d, uint64_t k) { return sum_level(d, k); }
 };
 template <> struct Game<K_TTT> {
+  static constexpr int kOwner = OWNER_FAST, kMaps = kSymTttMaps;
+  static constexpr KindFacts kFacts = {18, 3.0, true};
   static GM_HD int prim(const Desc& d, uint64_t k) { return ttt_prim(d, k); }
   template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return ttt_children(d, k, f); }
+  template <class F> static GM_HD int children_sym(const Desc& d, uint64_t k, F&& f) { return ttt_children_sym(d, k, f); }
   static GM_HD int level(const Desc& d, uint64_t k) { return ttt_level(d, k); }
 };
 template <> struct Game<K_TOOT> {
+  static constexpr int kOwner = OWNER_FAST, kMaps = 1;
+  static constexpr KindFacts kFacts = {13, 3.6, true};
   static GM_HD int prim(const Desc& d, uint64_t k) { return toot_prim(d, k); }
   template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return toot_children(d, k, f); }
+  template <class F> static GM_HD int children_sym(const Desc& d, uint64_t k, F&& f) { return toot_children_sym(d, k, f); }
   static GM_HD int level(const Desc& d, uint64_t k) { return toot_level(d, k); }
 };
-// compile-time toot boards (kernel instantiation ids, not descriptor kinds)
-constexpr int K_TOOT_6x4 = 64, K_TOOT_5x4 = 54, K_TOOT_4x4 = 44;
-template <> struct Game<K_TOOT_6x4> : TootFixed<6, 4> { static constexpr bool kFixed = true; };
-template <> struct Game<K_TOOT_5x4> : TootFixed<5, 4> { static constexpr bool kFixed = true; };
-template <> struct Game<K_TOOT_4x4> : TootFixed<4, 4> { static constexpr bool kFixed = true; };
+template <> struct Game<K_OTHELLO> {
+  static constexpr int kOwner = OWNER_FAST, kMaps = kSymOthMaps;
+  static constexpr KindFacts kFacts = {3, 2.0, true};
+  static GM_HD int prim(const Desc& d, uint64_t k) { return oth_prim(d, k); }
+  template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return oth_children(d, k, f); }
+  template <class F> static GM_HD int children_sym(const Desc& d, uint64_t k, F&& f) { return oth_children_sym(d, k, f); }
+  static GM_HD int level(const Desc& d, uint64_t k) { return oth_level(d, k); }
+};
 template <> struct Game<K_CONNECT> {
+  static constexpr int kOwner = OWNER_CONNECT, kMaps = 1;
+  static constexpr KindFacts kFacts = {0, 0.0, true};
   static GM_HD int prim(const Desc& d, uint64_t k) { return connect_prim(d, k); }
   template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return connect_children(d, k, f); }
+  template <class F> static GM_HD int children_sym(const Desc& d, uint64_t k, F&& f) { return connect_children_sym(d, k, f); }
   static GM_HD int level(const Desc& d, uint64_t k) { return connect_level(d, k); }
 };
-// compile-time connect-four boards, connect 4
+// compile-time boards (kernel instantiation ids, not descriptor kinds):
+// toot L x 4, and connect four with connect 4
+constexpr int K_TOOT_6x4 = 64, K_TOOT_5x4 = 54, K_TOOT_4x4 = 44;
+template <> struct Game<K_TOOT_6x4> : TootFixed<6, 4> {};
+template <> struct Game<K_TOOT_5x4> : TootFixed<5, 4> {};
+template <> struct Game<K_TOOT_4x4> : TootFixed<4, 4> {};
 constexpr int K_CONNECT_5x4 = 154, K_CONNECT_6x5 = 165;
-template <> struct Game<K_CONNECT_5x4> : ConnectFixed<5, 4, 4> { static constexpr bool kFixed = true; };
-template <> struct Game<K_CONNECT_6x5> : ConnectFixed<6, 5, 4> { static constexpr bool kFixed = true; };
+template <> struct Game<K_CONNECT_5x4> : ConnectFixed<5, 4, 4> {};
+template <> struct Game<K_CONNECT_6x5> : ConnectFixed<6, 5, 4> {};
 // the instantiation id for a descriptor: a fixed board where one exists
 GM_HD int fixed_kind(const Desc& d) {
   if (d.kind == K_TOOT && d.H == 4 && d.L >= 4 && d.L <= 6) return d.L * 10 + 4;
@@ -651,50 +699,50 @@ GM_HD int fixed_kind(const Desc& d) {
   if (d.kind == K_CONNECT && d.variant == 4 && d.L == 6 && d.H == 5) return K_CONNECT_6x5;
   return d.kind;
 }
-template <> struct Game<K_OTHELLO> {
-  static GM_HD int prim(const Desc& d, uint64_t k) { return oth_prim(d, k); }
-  template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return oth_children(d, k, f); }
-  static GM_HD int level(const Desc& d, uint64_t k) { return oth_level(d, k); }
-};
 
-// the kinds of a board-symmetric descriptor (Desc::bsym): the same rules,
-// children emitted as orbit representatives.  Instantiations of their own,
-// so that a solve without the parameter runs the kernels it always ran.
-constexpr int K_SYM = 256;
-constexpr int kind_base(int kind) { return kind & ~K_SYM; }
-template <> struct Game<K_TTT | K_SYM> : Game<K_TTT> {
-  template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return ttt_children_sym(d, k, f); }
-};
-template <> struct Game<K_TOOT | K_SYM> : Game<K_TOOT> {
-  template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return toot_children_sym(d, k, f); }
-};
-template <> struct Game<K_TOOT_6x4 | K_SYM> : Game<K_TOOT_6x4> {
-  template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return children_sym(d, k, f); }
-};
-template <> struct Game<K_TOOT_5x4 | K_SYM> : Game<K_TOOT_5x4> {
-  template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return children_sym(d, k, f); }
-};
-template <> struct Game<K_TOOT_4x4 | K_SYM> : Game<K_TOOT_4x4> {
-  template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return children_sym(d, k, f); }
-};
-template <> struct Game<K_OTHELLO | K_SYM> : Game<K_OTHELLO> {
-  template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return oth_children_sym(d, k, f); }
-};
-template <> struct Game<K_CONNECT | K_SYM> : Game<K_CONNECT> {
-  template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return connect_children_sym(d, k, f); }
-};
-template <> struct Game<K_CONNECT_5x4 | K_SYM> : Game<K_CONNECT_5x4> {
-  template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return children_sym(d, k, f); }
-};
-template <> struct Game<K_CONNECT_6x5 | K_SYM> : Game<K_CONNECT_6x5> {
-  template <class F> static GM_HD int children(const Desc& d, uint64_t k, F&& f) { return children_sym(d, k, f); }
-};
-// an instantiation id of connect four (generic or fixed, plain or symmetric)
-constexpr bool kind_is_connect(int kind) {
-  return kind_base(kind) == K_CONNECT || kind_base(kind) == K_CONNECT_5x4 || kind_base(kind) == K_CONNECT_6x5;
+// The kind lists: each holds exactly the ids its path instantiates kernels
+// for, and its LAST member also serves any id the list does not hold.
+template <int... Ks> struct KindList {};
+using GenericKinds = KindList<K_SUM, K_TTT, K_TOOT, K_CONNECT, K_OTHELLO>;  // HASHED, the keyed shards
+using BucketedKinds = KindList<K_TTT, K_TOOT_6x4, K_TOOT_5x4, K_TOOT_4x4, K_TOOT, K_CONNECT_5x4, K_CONNECT_6x5,
+                               K_CONNECT, K_OTHELLO>;  // by fixed_kind
+using RankedKinds = KindList<K_TOOT_6x4, K_TOOT_5x4, K_TOOT_4x4, K_TOOT>;  // by fixed_kind
+
+// fn(std::integral_constant<int, K>{}) for the member K == id of the list
+template <class Fn, int... Ks>
+inline void kind_dispatch_list(KindList<Ks...>, int id, Fn&& fn) {
+  constexpr int ks[] = {Ks...}, last = ks[sizeof...(Ks) - 1];
+  const bool hit = ((id == Ks && (fn(std::integral_constant<int, Ks>{}), true)) || ...);
+  if (!hit) fn(std::integral_constant<int, last>{});
 }
-// the instantiation id with the symmetric form where the descriptor asks
-GM_HD int sym_kind(const Desc& d, int kind) { return d.bsym ? (kind | K_SYM) : kind; }
+template <class List, class Fn>
+inline void kind_dispatch(int id, Fn&& fn) { kind_dispatch_list(List{}, id, fn); }
+// the same with the symmetric id (K | K_SYM) where the descriptor asks for
+// orbit representatives; kernels that never generate children take the plain
+// one, the symmetric kinds differing in `children` alone
+template <class List, class Fn>
+inline void kind_dispatch_sym(const Desc& d, int id, Fn&& fn) {
+  kind_dispatch<List>(id, [&](auto kind_) {
+    constexpr int K = decltype(kind_)::value;
+    if constexpr (Game<K>::kMaps > 0) {
+      if (d.bsym) return fn(std::integral_constant<int, K | K_SYM>{});
+    }
+    fn(kind_);
+  });
+}
+
+// a descriptor kind's host facts
+inline KindFacts kind_facts(int kind) {
+  KindFacts f{};
+  kind_dispatch<GenericKinds>(kind, [&](auto kind_) { f = Game<decltype(kind_)::value>::kFacts; });
+  return f;
+}
+// maps of the descriptor's board group (identity excluded); 0: no group here
+inline int sym_board_maps(const Desc& d) {
+  int n = 0;
+  kind_dispatch<GenericKinds>(d.kind, [&](auto kind_) { n = Game<decltype(kind_)::value>::kMaps; });
+  return n;
+}
 
 GM_HD int any_prim(const Desc& d, uint64_t k) {
   switch (d.kind) {

@@ -195,9 +195,9 @@ __device__ __forceinline__ uint32_t owner_dev(const Desc& d, u64 key, uint32_t P
 // occupancy)
 template <int KIND>
 __device__ __forceinline__ uint32_t owner_k(const Desc& d, u64 key, uint32_t P) {
-  if constexpr (kind_is_connect(KIND))
+  if constexpr (Game<KIND>::kOwner == OWNER_CONNECT)
     return owner_connect(d.A, key, P);
-  else if constexpr (kind_base(KIND) != K_SUM)  // the board games, plain or symmetric
+  else if constexpr (Game<KIND>::kOwner == OWNER_FAST)  // the other board games, plain or symmetric
     return owner_fast(d, key, P);
   else
     return owner_dev(d, key, P);
@@ -211,9 +211,9 @@ __device__ __noinline__ uint32_t owner_fast_call(const OwnerGeom d, u64 key, uin
 // as a call, for a kernel specialised to KIND (no scratch-array path for the fast kinds)
 template <int KIND>
 __device__ __forceinline__ uint32_t owner_call_k(const Desc& d, u64 key, uint32_t P) {
-  if constexpr (kind_is_connect(KIND))
+  if constexpr (Game<KIND>::kOwner == OWNER_CONNECT)
     return owner_connect_call(d.A, key, P);
-  else if constexpr (kind_base(KIND) != K_SUM)  // the board games, plain or symmetric
+  else if constexpr (Game<KIND>::kOwner == OWNER_FAST)  // the other board games, plain or symmetric
     return owner_fast_call(OwnerGeom{d.kind, d.variant, d.A, d.nbits}, key, P);
   else
     return owner_of_call(d, key, P);

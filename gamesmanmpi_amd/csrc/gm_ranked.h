@@ -1033,16 +1033,6 @@ static int rank_setup(gm_solver* s, const gm_buffers* buf) {
   return 0;
 }
 
-template <class F>
-static void rank_kind_dispatch(const Desc& d, F&& f) {
-  switch (fixed_kind(d)) {
-    case K_TOOT_6x4: f(std::integral_constant<int, K_TOOT_6x4>()); break;
-    case K_TOOT_5x4: f(std::integral_constant<int, K_TOOT_5x4>()); break;
-    case K_TOOT_4x4: f(std::integral_constant<int, K_TOOT_4x4>()); break;
-    default: f(std::integral_constant<int, K_TOOT>()); break;
-  }
-}
-
 // GM_RK_DBG=1 / 2: the backward without its gathers / without its entries
 // (timing A/B only: the words are wrong)
 static int rk_dbg() {
@@ -1061,7 +1051,7 @@ static int rank_grid(const gm_solver* s, u64 nitems) {
 static void rank_forward_level(gm_solver* s, hipStream_t st, uint32_t L) {
   const Desc& d = s->d;
   const RankGeom& g = s->rg;
-  rank_kind_dispatch(d, [&](auto KC) {
+  kind_dispatch<RankedKinds>(fixed_kind(d), [&](auto KC) {
     constexpr int KIND = decltype(KC)::value;
     const u64 nreal = s->rlvitems[L] >> 3, nb = (s->rlvstart[L + 1] - s->rlvstart[L]) >> 3;  // boards
     auto boards = [&](auto CH) {

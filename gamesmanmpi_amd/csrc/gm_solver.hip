@@ -5,7 +5,7 @@
 //
 //   gm_codec.h gm_games.h gm_md5.h  keys, the games' moves, md5 owners
 //   gm_plane.h           PLANES kernels
-//   (here)               errors, SolveEvents, the game registry, the dense /
+//   (here)               errors, SolveEvents, gm_registry.h (host), the dense /
 //                        halo / group / column geometry, DevState, the HASHED
 //                        kernels (k_seed, k_expand, k_finalize, k_resolve, ...)
 //   gm_dense.h           DENSE kernels
@@ -192,196 +192,7 @@ enum : uint32_t {
   ERR_PLANE_STALL = 1024u,
 };
 
-// ---------------------------------------------------------------------------
-// game registry
-// ---------------------------------------------------------------------------
-static std::mutex g_mu;
-static std::vector<Desc> g_games;
-
-
-static int kv(const char* params, const char* key, int dflt) {
-  if (!params) return dflt;
-  size_t kl = strlen(key);
-  for (const char* p = params; (p = strstr(p, key)); p += kl) {
-    if ((p == params || p[-1] == ',') && p[kl] == '=') return atoi(p + kl + 1);
-  }
-  return dflt;
-}
-
-static int build_desc(const char* name, const char* params, Desc* out) {
-  Desc d;
-  memset(&d, 0, sizeof d);
-  if (!strcmp(name, "four_to_one") || !strcmp(name, "sum_four_to_one")) {
-    d.kind = K_SUM;
-    if (name[0] == 'f') {
-      d.variant = 1;
-      int start = kv(params, "start", 4);  // four_to_one.py:7-8
-      if (start < 0) return fail(GM_EINVAL, "four_to_one start must be >= 0");
-      d.nheaps = 1;
-      d.heap[0] = (uint32_t)start;
-    } else {
-      const char* p = params ? strstr(params, "heaps=") : nullptr;
-      if (!p) return fail(GM_EINVAL, "sum_four_to_one needs heaps=h0:h1:...");
-      p += 6;
-      while (*p && *p != ',') {
-        if (d.nheaps >= 16) return fail(GM_EINVAL, "at most 16 heaps");
-        long h = strtol(p, nullptr, 10);
-        if (h < 0 || h > (1L << 30)) return fail(GM_EINVAL, "bad heap %ld", h);
-        d.heap[d.nheaps++] = (uint32_t)h;
-        while (*p && *p != ':' && *p != ',') p++;
-        if (*p == ':') p++;
-      }
-      if (d.nheaps == 0) return fail(GM_EINVAL, "no heaps");
-    }
-    unsigned __int128 stride = 1;
-    d.pow2 = 1;
-    d.root = 0;
-    d.root_sum = 0;
-    for (int i = 0; i < d.nheaps; i++) {
-      d.base[i] = d.heap[i] + 1;
-      d.stride[i] = (uint64_t)stride;
-      if (d.base[i] & (d.base[i] - 1)) d.pow2 = 0;
-      int sh = 0;
-      while ((1ull << sh) < (uint64_t)stride) sh++;
-      d.shift[i] = (uint32_t)sh;
-      d.root += (uint64_t)d.heap[i] * d.stride[i];
-      d.root_sum += d.heap[i];
-      stride *= d.base[i];
-      if (stride > ((unsigned __int128)1 << 62)) return fail(GM_EINVAL, "state space exceeds 2^62");
-    }
-    if (d.root_sum >= (1u << 30) - 2) return fail(GM_EINVAL, "remoteness would exceed 30 bits");
-    d.max_levels = (int)d.root_sum + 1;
-    // dense layout (see gm_dense.h)
-    d.W = 1;
-    for (int i = 1; i < d.nheaps; i++) {
-      d.pstride[i] = d.W;
-      int sh = 0;
-      while ((1ull << sh) < d.W) sh++;
-      d.pshift[i] = (uint32_t)sh;
-      d.W *= d.base[i];
-    }
-    d.wshift = -1;
-    if ((d.W & (d.W - 1)) == 0) {
-      int sh = 0;
-      while ((1ull << sh) < d.W) sh++;
-      d.wshift = sh;
-    }
-    d.dense_ok = 1;
-  } else if (!strcmp(name, "tic_tac_toe_np") || !strcmp(name, "mttt")) {
-    d.kind = K_TTT;
-    d.variant = name[0] == 'm';
-    d.root = 0;
-    d.max_levels = 10;
-  } else if (!strcmp(name, "toot_and_otto_bitstring")) {
-    d.kind = K_TOOT;
-    d.L = kv(params, "length", 6);  // toot_and_otto_bitstring.py:8
-    d.H = kv(params, "height", 4);
-    d.A = d.L * d.H;
-    if (d.L < 1 || d.H < 1 || 2 * d.A + 13 > 64)
-      return fail(GM_EINVAL, "toot board %dx%d does not fit a 64-bit key (area <= 25)", d.L, d.H);
-    d.nbits = (2 * d.A + 17 + 7) / 8 * 8;
-    d.full = (1ull << d.A) - 1;
-    for (int y = 0; y < d.H; y++) d.col0 |= 1ull << (d.L * y);
-    // word starts per direction: (1,0) (0,1) (1,1) (1,-1); steps in cell index
-    const int dxs[4] = {1, 0, 1, 1}, dys[4] = {0, 1, 1, -1};
-    for (int i = 0; i < 4; i++) {
-      uint64_t m = 0;
-      for (int x = 0; x < d.L; x++)
-        for (int y = 0; y < d.H; y++) {
-          int ex = x + 3 * dxs[i], ey = y + 3 * dys[i];
-          if (ex >= 0 && ex < d.L && ey >= 0 && ey < d.H) m |= 1ull << (d.L * y + x);
-        }
-      d.tmask[i] = m;
-      d.tstep[i] = dxs[i] + d.L * dys[i];
-    }
-    // initial_position (:36-44): hands 6,6,6,6; turn bit 0 (player 2 first)
-    d.root = 0;
-    for (int j = 0; j < 4; j++) d.root |= 6ull << (2 * d.A + 3 * j);
-    d.max_levels = d.A + 1;
-  } else if (!strcmp(name, "othello_bit_new")) {
-    d.kind = K_OTHELLO;
-    d.L = kv(params, "length", 8);  // othello_bit_new.py:8
-    d.H = kv(params, "height", 8);
-    d.A = d.L * d.H;
-    if (d.L != d.H)
-      return fail(GM_EINVAL, "othello descriptor supports square boards only (reference flip bounds "
-                             "are transposed for non-square boards, othello_bit_new.py:101,110)");
-    if (d.L < 2 || 2 * d.A + 3 > 64)
-      return fail(GM_EINVAL, "othello board %dx%d does not fit a 64-bit key (area <= 30)", d.L, d.H);
-    d.nbits = (2 * d.A + 16 + 7) / 8 * 8;
-    d.full = (1ull << d.A) - 1;
-    // initial_position (:37-48) with the module's float coordinates
-    // (length / 2 - 1): board index int(length*y + x)
-    auto put = [&](double x, double y, int white) {
-      int idx = (int)(d.L * y + x);
-      d.root |= 1ull << (white ? idx : d.A + idx);
-    };
-    double hx = d.L / 2.0, hy = d.H / 2.0;
-    d.root = 0;
-    put(hx - 1, hy - 1, 1);
-    put(hx - 1, hy, 0);
-    put(hx, hy - 1, 0);
-    put(hx, hy, 1);
-    // two incr_turn calls from 0 -> turn_count 2 (WHITE): bit 2A = 0
-    d.max_levels = d.A + 3;
-    d.sym = kv(params, "symmetry", 0) ? 1 : 0;  // player_flip orbits (symmetry_functions, :224-226)
-    d.root = oth_canon(d, d.root);
-  } else if (!strcmp(name, "connect_four")) {
-    d.kind = K_CONNECT;
-    d.L = kv(params, "length", 5);  // games/connect_four.py
-    d.H = kv(params, "height", 4);
-    d.variant = kv(params, "connect", 4);
-    if (d.L < 1 || d.H < 1 || d.L > 8 || (long)d.L * d.H > 30)
-      return fail(GM_EINVAL, "connect four board %dx%d: at most 8 columns and 30 cells fit the key "
-                             "(two planes of L*H bits; 7x6 is out of reach)", d.L, d.H);
-    d.A = d.L * d.H;
-    if (d.variant < 1 || d.variant > (d.L > d.H ? d.L : d.H))
-      return fail(GM_EINVAL, "connect=%d: a line on a %dx%d board has 1..%d cells", d.variant, d.L, d.H,
-                  d.L > d.H ? d.L : d.H);
-    d.full = (1ull << d.A) - 1;
-    for (int y = 0; y < d.H; y++) d.col0 |= 1ull << (d.L * y);
-    // line starts per direction: (1,0) (0,1) (1,1) (1,-1); a start cell's
-    // whole line is on the board, so no shifted copy wraps a row
-    const int dxs[4] = {1, 0, 1, 1}, dys[4] = {0, 1, 1, -1};
-    for (int i = 0; i < 4; i++) {
-      uint64_t m = 0;
-      for (int x = 0; x < d.L; x++)
-        for (int y = 0; y < d.H; y++) {
-          int ex = x + (d.variant - 1) * dxs[i], ey = y + (d.variant - 1) * dys[i];
-          if (ex >= 0 && ex < d.L && ey >= 0 && ey < d.H) m |= 1ull << (d.L * y + x);
-        }
-      d.tmask[i] = m;
-      d.tstep[i] = dxs[i] + d.L * dys[i];
-    }
-    d.root = 0;
-    d.max_levels = d.A + 1;
-  } else {
-    return fail(GM_EINVAL, "no device descriptor for game '%s'", name);
-  }
-  if (kv(params, "symmetry", 0) && d.kind != K_OTHELLO)
-    return fail(GM_EINVAL, "'%s' defines no symmetry_functions() to reduce by", name);
-  if (kv(params, "board_symmetry", 0)) {  // orbit representatives under the board's group (gm_sym.h)
-    if (d.kind == K_SUM)
-      return fail(GM_EINVAL, "'%s' has no board: board_symmetry=1 covers tic-tac-toe, toot-and-otto, othello and connect four "
-                             "(heap permutations are not implemented)", name);
-    if (kv(params, "symmetry", 0))
-      return fail(GM_EINVAL, "board_symmetry=1 and symmetry=1 do not combine: player_flip swaps the colours "
-                             "the board maps keep");
-    d.bsym = 1;
-    if (d.kind == K_TOOT || d.kind == K_CONNECT) {  // the same two planes of H rows
-      d.nmir = d.L / 2;
-      for (int i = 0; i < d.nmir; i++) d.mir[i] = sym_toot_mask(d.L, d.H, i);
-    }
-    // every map fixes the start position, so the group acts on the reachable
-    // set and the root is its own representative
-    for (int i = 0; i < sym_board_maps(d); i++)
-      if (sym_board_map(d, d.root, i) != d.root)
-        return fail(GM_EINVAL, "board map %d of '%s' moves the start position of this board", i, name);
-    if (sym_board_canon(d, d.root) != d.root) return fail(GM_EINVAL, "the root of '%s' is not its own representative", name);
-  }
-  *out = d;
-  return 0;
-}
+#include "gm_registry.h"
 
 // Shard geometry of a dense table.  world == 1: the whole prefix space.
 // world > 1: the values [0, E) of the TOP prefix digit (heap K-1) are cut
@@ -449,12 +260,6 @@ static u64 dense_bits_bytes(const Desc* d, const DenseGeom& g) {
   return (u64)d->max_levels * g.v.Wbl / 8;
 }
 
-
-static const Desc* get_game(int id) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  if (id < 0 || id >= (int)g_games.size()) return nullptr;
-  return &g_games[id];
-}
 
 // ---------------------------------------------------------------------------
 // device helpers
@@ -1170,45 +975,19 @@ static int launch_grid() {
   return g;
 }
 
-template <int KIND>
-static void enqueue_level_expand(gm_solver* s, int L) {
-  hipLaunchKernelGGL(k_expand<KIND>, dim3(s->grid), dim3(kBlock), 0, s->stream, s->d, s->tab, s->mask, s->lv,
-                     s->lcap, s->st, L);
-}
-template <int KIND>
-static void enqueue_level_resolve(gm_solver* s, int L) {
-  hipLaunchKernelGGL(k_resolve<KIND>, dim3(s->grid), dim3(kBlock), 0, s->stream, s->d, s->tab, s->mask, s->lv,
-                     s->lcap, s->st, L);
-}
+// one HASHED level: the kernel of the descriptor's kind, symmetric where it
+// asks for orbit representatives (gm_sym.h)
 static void do_expand(gm_solver* s, int L) {
-  if (s->d.bsym) switch (s->d.kind) {  // children as orbit representatives (gm_sym.h)
-    case K_TTT: return enqueue_level_expand<K_TTT | K_SYM>(s, L);
-    case K_TOOT: return enqueue_level_expand<K_TOOT | K_SYM>(s, L);
-    case K_CONNECT: return enqueue_level_expand<K_CONNECT | K_SYM>(s, L);
-    default: return enqueue_level_expand<K_OTHELLO | K_SYM>(s, L);
-  }
-  switch (s->d.kind) {
-    case K_SUM: enqueue_level_expand<K_SUM>(s, L); break;
-    case K_TTT: enqueue_level_expand<K_TTT>(s, L); break;
-    case K_TOOT: enqueue_level_expand<K_TOOT>(s, L); break;
-    case K_CONNECT: enqueue_level_expand<K_CONNECT>(s, L); break;
-    default: enqueue_level_expand<K_OTHELLO>(s, L); break;
-  }
+  kind_dispatch_sym<GenericKinds>(s->d, s->d.kind, [&](auto kind_) {
+    hipLaunchKernelGGL(k_expand<decltype(kind_)::value>, dim3(s->grid), dim3(kBlock), 0, s->stream, s->d, s->tab, s->mask,
+                       s->lv, s->lcap, s->st, L);
+  });
 }
 static void do_resolve(gm_solver* s, int L) {
-  if (s->d.bsym) switch (s->d.kind) {
-    case K_TTT: return enqueue_level_resolve<K_TTT | K_SYM>(s, L);
-    case K_TOOT: return enqueue_level_resolve<K_TOOT | K_SYM>(s, L);
-    case K_CONNECT: return enqueue_level_resolve<K_CONNECT | K_SYM>(s, L);
-    default: return enqueue_level_resolve<K_OTHELLO | K_SYM>(s, L);
-  }
-  switch (s->d.kind) {
-    case K_SUM: enqueue_level_resolve<K_SUM>(s, L); break;
-    case K_TTT: enqueue_level_resolve<K_TTT>(s, L); break;
-    case K_TOOT: enqueue_level_resolve<K_TOOT>(s, L); break;
-    case K_CONNECT: enqueue_level_resolve<K_CONNECT>(s, L); break;
-    default: enqueue_level_resolve<K_OTHELLO>(s, L); break;
-  }
+  kind_dispatch_sym<GenericKinds>(s->d, s->d.kind, [&](auto kind_) {
+    hipLaunchKernelGGL(k_resolve<decltype(kind_)::value>, dim3(s->grid), dim3(kBlock), 0, s->stream, s->d, s->tab,
+                       s->mask, s->lv, s->lcap, s->st, L);
+  });
 }
 
 static std::string err_text(uint32_t e) {
@@ -1326,133 +1105,12 @@ int gm_abi_sizes(uint32_t out[3]) {
   return 0;
 }
 
-int gm_game_lookup(const char* name, const char* params, int* game_id) {
-  if (!name || !game_id) return fail(GM_EINVAL, "null argument");
-  Desc d;
-  int rc = build_desc(name, params ? params : "", &d);
-  if (rc) return rc;
-  std::lock_guard<std::mutex> lk(g_mu);
-  for (size_t i = 0; i < g_games.size(); i++)
-    if (!memcmp(&g_games[i], &d, sizeof d)) { *game_id = (int)i; return 0; }
-  g_games.push_back(d);
-  *game_id = (int)g_games.size() - 1;
-  return 0;
-}
-
-// boards of L columns of 0..H pieces with n pieces in all, times the ways to
-// colour them with ceil(n/2) X and floor(n/2) O, summed over n (L*H <= 30:
-// every term fits 64 bits)
-static uint64_t connect_fillings(int L, int H) {
-  const int A = L * H;
-  uint64_t ways[31] = {1}, choose[31][31] = {};
-  for (int c = 0; c < L; c++) {  // one column more: heights 0..H
-    uint64_t next[31] = {};
-    for (int n = 0; n <= A; n++)
-      for (int h = 0; h <= H && n + h <= A; h++) next[n + h] += ways[n];
-    memcpy(ways, next, sizeof ways);
-  }
-  for (int n = 0; n <= A; n++) {
-    choose[n][0] = 1;
-    for (int r = 1; r <= n; r++) choose[n][r] = choose[n - 1][r - 1] + (r <= n - 1 ? choose[n - 1][r] : 0);
-  }
-  uint64_t total = 0;
-  for (int n = 0; n <= A; n++) total += ways[n] * choose[n][n / 2];
-  return total;
-}
-
-int gm_game_info(int game, uint64_t* positions_bound, uint32_t* max_levels, uint32_t* key_bits) {
-  const Desc* d = get_game(game);
-  if (!d) return fail(GM_EINVAL, "bad game id %d", game);
-  uint64_t bound = 0;
-  uint32_t bits = 0;
-  switch (d->kind) {
-    case K_SUM: {
-      unsigned __int128 p = 1;
-      for (int i = 0; i < d->nheaps; i++) p *= d->base[i];
-      bound = (uint64_t)p;
-      bits = 64 - __builtin_clzll(bound | 1);
-      break;
-    }
-    case K_TTT: bound = 5478; bits = 18; break;
-    case K_TOOT: {
-      // reachable counts measured by the survey (Appendix B) where known
-      if (d->L == 3 && d->H == 3) bound = 11097;
-      else if (d->L == 4 && d->H == 3) bound = 200127;
-      else if (d->L == 3 && d->H == 4) bound = 126559;
-      else if (d->L == 4 && d->H == 4) bound = 3468773;
-      else if (d->L == 5 && d->H == 4) bound = 70184763;
-      else if (d->L == 6 && d->H == 4) bound = 1187212827ull;
-      else bound = 0;  // unknown: caller must pass an estimate to gm_plan
-      bits = 2 * d->A + 13;
-      break;
-    }
-    case K_CONNECT:
-      // the enumerated (and published) counts where known, else the gravity
-      // fillings with balanced colours, wins ignored: a true upper bound
-      if (d->L == 4 && d->H == 4 && d->variant == 4) bound = 161029;
-      else if (d->L == 5 && d->H == 4 && d->variant == 4) bound = 3945711;
-      else bound = connect_fillings(d->L, d->H);
-      bits = 2 * d->A;
-      break;
-    default:
-      if (d->L == 4) bound = 54089;
-      else bound = 0;
-      bits = 2 * d->A + 3;
-  }
-  if (positions_bound) *positions_bound = bound;
-  if (max_levels) *max_levels = (uint32_t)d->max_levels;
-  if (key_bits) *key_bits = bits;
-  return 0;
-}
-
-int gm_root(int game, uint64_t* key) {
-  const Desc* d = get_game(game);
-  if (!d || !key) return fail(GM_EINVAL, "bad game id %d", game);
-  *key = d->root;
-  return 0;
-}
-
+// (gm_game_lookup, gm_game_info, gm_root: gm_registry.h)
 int gm_encode(int game, const uint8_t* canon, size_t n, uint64_t* key) {
   const Desc* d = get_game(game);
   if (!d || !canon || !key) return fail(GM_EINVAL, "bad argument");
-  if (d->kind == K_TOOT || d->kind == K_OTHELLO) {
-    if (key_from_bits(*d, canon, (int)n, key)) return fail(GM_EINVAL, "bytes are not a %s position", d->kind == K_TOOT ? "toot" : "othello");
-    return 0;
-  }
-  if (d->kind == K_CONNECT) {
-    if (connect_key_from_chars(*d, canon, (int)n, key))
-      return fail(GM_EINVAL, "connect four positions are %d characters of - X O", d->A);
-    return 0;
-  }
-  if (d->kind == K_TTT) {
-    if (n != 9) return fail(GM_EINVAL, "tic-tac-toe positions are 9 bytes");
-    uint64_t k = 0;
-    for (int c = 0; c < 9; c++) {
-      uint32_t v;
-      if (d->variant == 1) {
-        if (canon[c] == '_') v = 0;
-        else if (canon[c] == 'X') v = 1;
-        else if (canon[c] == 'O') v = 2;
-        else return fail(GM_EINVAL, "mttt cell must be _ X or O");
-      } else {
-        if (canon[c] > 2) return fail(GM_EINVAL, "tic_tac_toe_np cell must be 0, 1 or 2");
-        v = canon[c];
-      }
-      k |= (uint64_t)v << (2 * c);
-    }
-    *key = k;
-    return 0;
-  }
-  if (n == 0 || n > 20) return fail(GM_EINVAL, "bad integer position");
-  unsigned __int128 v = 0;
-  for (size_t i = 0; i < n; i++) {
-    if (canon[i] < '0' || canon[i] > '9') return fail(GM_EINVAL, "integer positions are non-negative decimals");
-    v = v * 10 + (canon[i] - '0');
-  }
-  unsigned __int128 space = 1;
-  for (int i = 0; i < d->nheaps; i++) space *= d->base[i];
-  if (v >= space) return fail(GM_EINVAL, "position outside the game's state space");
-  *key = (uint64_t)v;
+  char why[96];
+  if (key_from_canon(*d, canon, n, key, why)) return fail(GM_EINVAL, "%s", why);
   return 0;
 }
 
@@ -2442,29 +2100,16 @@ int gm_owner(int game, const uint64_t* keys_dev, uint64_t n, int world_size, uin
 // md5-sharded keyed tables (gm_keyed_shard.h): the host moves keys/words
 // between ranks between these steps (gamesmanmpi_amd/keyed.py)
 // ---------------------------------------------------------------------------
-#define GM_KIND_CASE(KERNEL, K, GRID, S, ...) \
-  case K: hipLaunchKernelGGL(KERNEL<K>, dim3(GRID), dim3(kBlock), 0, (S)->stream, __VA_ARGS__); break;
-#define GM_KIND_DISPATCH(KERNEL, GRID, S, ...)                        \
-  switch (sym_kind((S)->d, (S)->d.kind)) {                           \
-    GM_KIND_CASE(KERNEL, K_SUM, GRID, S, __VA_ARGS__)                 \
-    GM_KIND_CASE(KERNEL, K_TTT, GRID, S, __VA_ARGS__)                 \
-    GM_KIND_CASE(KERNEL, K_TOOT, GRID, S, __VA_ARGS__)                \
-    GM_KIND_CASE(KERNEL, K_OTHELLO, GRID, S, __VA_ARGS__)             \
-    GM_KIND_CASE(KERNEL, K_CONNECT, GRID, S, __VA_ARGS__)             \
-    GM_KIND_CASE(KERNEL, K_TTT | K_SYM, GRID, S, __VA_ARGS__)         \
-    GM_KIND_CASE(KERNEL, K_TOOT | K_SYM, GRID, S, __VA_ARGS__)        \
-    GM_KIND_CASE(KERNEL, K_OTHELLO | K_SYM, GRID, S, __VA_ARGS__)     \
-    GM_KIND_CASE(KERNEL, K_CONNECT | K_SYM, GRID, S, __VA_ARGS__)     \
-  }
-// kernels that never generate children (k_ks_insert, k_ks_reduce)
-#define GM_KIND_DISPATCH_PLAIN(KERNEL, GRID, S, ...)                  \
-  switch ((S)->d.kind) {                                             \
-    GM_KIND_CASE(KERNEL, K_SUM, GRID, S, __VA_ARGS__)                 \
-    GM_KIND_CASE(KERNEL, K_TTT, GRID, S, __VA_ARGS__)                 \
-    GM_KIND_CASE(KERNEL, K_TOOT, GRID, S, __VA_ARGS__)                \
-    GM_KIND_CASE(KERNEL, K_OTHELLO, GRID, S, __VA_ARGS__)             \
-    GM_KIND_CASE(KERNEL, K_CONNECT, GRID, S, __VA_ARGS__)             \
-  }
+// (GM_KS_LAUNCH_PLAIN: kernels that never generate children -- k_ks_insert,
+// k_ks_reduce)
+#define GM_KS_LAUNCH(KERNEL, GRID, S, ...)                                                                  \
+  kind_dispatch_sym<GenericKinds>((S)->d, (S)->d.kind, [&](auto kind_) {                                    \
+    hipLaunchKernelGGL(KERNEL<decltype(kind_)::value>, dim3(GRID), dim3(kBlock), 0, (S)->stream, __VA_ARGS__); \
+  })
+#define GM_KS_LAUNCH_PLAIN(KERNEL, GRID, S, ...)                                                            \
+  kind_dispatch<GenericKinds>((S)->d.kind, [&](auto kind_) {                                                \
+    hipLaunchKernelGGL(KERNEL<decltype(kind_)::value>, dim3(GRID), dim3(kBlock), 0, (S)->stream, __VA_ARGS__); \
+  })
 
 static int ks_check(gm_solver* s, int level) {
   if (!s) return fail(GM_EINVAL, "null solver");
@@ -2518,7 +2163,7 @@ int gm_ks_expand(gm_solver* s, int level, uint64_t* keys_dev, uint32_t* owners_d
   uint64_t width = 0;
   if ((rc = gm_ks_level_size(s, level, &width))) return rc;
   HIPCHK(hipMemsetAsync(&s->st->ks_cursor, 0, sizeof(u64), s->stream));
-  GM_KIND_DISPATCH(k_ks_expand, ks_grid(s, width), s, s->d, s->lv, s->lcap, s->st, level, (u64*)keys_dev, cap,
+  GM_KS_LAUNCH(k_ks_expand, ks_grid(s, width), s, s->d, s->lv, s->lcap, s->st, level, (u64*)keys_dev, cap,
                    &s->st->ks_cursor);
   HIPCHK(hipGetLastError());
   u64 got = 0;
@@ -2538,7 +2183,7 @@ int gm_ks_insert(gm_solver* s, int level, const uint64_t* keys_dev, uint64_t n) 
   int rc = ks_check(s, level);
   if (rc) return rc;
   if (n && !keys_dev) return fail(GM_EINVAL, "null keys");
-  if (n) GM_KIND_DISPATCH_PLAIN(k_ks_insert, ks_grid(s, n), s, s->d, s->tab, s->mask, s->lv, s->lcap, s->st, level,
+  if (n) GM_KS_LAUNCH_PLAIN(k_ks_insert, ks_grid(s, n), s, s->d, s->tab, s->mask, s->lv, s->lcap, s->st, level,
                           (const u64*)keys_dev, (u64)n);
   HIPCHK(hipGetLastError());
   return 0;
@@ -2560,7 +2205,7 @@ int gm_ks_counts(gm_solver* s, int level, uint64_t* counts_dev) {
   if ((rc = gm_ks_level_size(s, level, &width))) return rc;
   if (!width) return 0;
   if (!counts_dev) return fail(GM_EINVAL, "null counts");
-  GM_KIND_DISPATCH(k_ks_counts, ks_grid(s, width), s, s->d, s->lv, s->lcap, s->st, level, counts_dev);
+  GM_KS_LAUNCH(k_ks_counts, ks_grid(s, width), s, s->d, s->lv, s->lcap, s->st, level, counts_dev);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2573,7 +2218,7 @@ int gm_ks_children(gm_solver* s, int level, const uint64_t* offsets_dev, uint64_
   if ((rc = gm_ks_level_size(s, level, &width))) return rc;
   if (!width) return 0;
   if (!offsets_dev || !keys_dev || !owners_dev || world < 1) return fail(GM_EINVAL, "bad argument");
-  GM_KIND_DISPATCH(k_ks_children, ks_grid(s, width), s, s->d, s->lv, s->lcap, s->st, level, offsets_dev,
+  GM_KS_LAUNCH(k_ks_children, ks_grid(s, width), s, s->d, s->lv, s->lcap, s->st, level, offsets_dev,
                    (u64*)keys_dev, owners_dev, (uint32_t)world);
   HIPCHK(hipGetLastError());
   return 0;
@@ -2586,7 +2231,7 @@ int gm_ks_reduce(gm_solver* s, int level, const uint64_t* offsets_dev, const uin
   if ((rc = gm_ks_level_size(s, level, &width))) return rc;
   if (!width) return 0;
   if (!offsets_dev || !child_words_dev) return fail(GM_EINVAL, "bad argument");
-  GM_KIND_DISPATCH_PLAIN(k_ks_reduce, ks_grid(s, width), s, s->d, s->tab, s->mask, s->lv, s->lcap, s->st, level,
+  GM_KS_LAUNCH_PLAIN(k_ks_reduce, ks_grid(s, width), s, s->d, s->tab, s->mask, s->lv, s->lcap, s->st, level,
                    offsets_dev, child_words_dev);
   HIPCHK(hipGetLastError());
   return ks_errors(s);

@@ -130,10 +130,7 @@ GM_HD uint64_t sym_oth_canon(const Desc& d, uint64_t k) {
 }
 
 // ---- any game -------------------------------------------------------------
-// maps of the descriptor's board group (identity excluded); 0: no group here
-GM_HD int sym_board_maps(const Desc& d) {
-  return d.kind == K_TTT ? kSymTttMaps : (d.kind == K_TOOT || d.kind == K_CONNECT) ? 1 : d.kind == K_OTHELLO ? kSymOthMaps : 0;
-}
+// (the number of maps per kind: Game<K>::kMaps, sym_board_maps in gm_games.h)
 GM_HD uint64_t sym_board_map(const Desc& d, uint64_t k, int which) {
   if (d.kind == K_TTT) return sym_ttt_map(k, which);
   if (d.kind == K_TOOT || d.kind == K_CONNECT) return sym_toot_mirror(d, k);
