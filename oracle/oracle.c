@@ -403,7 +403,7 @@ static void ot_root(const game *g, blob *s) { /* initial_position :36-55 */
 /* ------------------------------------------------------------------------ */
 /* Game registry                                                             */
 /* ------------------------------------------------------------------------ */
-#define MAXGAMES 64
+#define MAXGAMES 512 /* distinct (name, params) of one process: the whole GPU suite asks for more than 64 */
 static game g_games[MAXGAMES];
 static int g_ngames;
 
