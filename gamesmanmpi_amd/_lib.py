@@ -34,6 +34,7 @@ GM_F_PLANE_NO_RUNS = 8192  # PLANES A/B: no one-workgroup runs of narrow levels 
 GM_F_BKS_LOCAL = 16384  # md5-sharded bucketed: local dedup before hashing / sending
 GM_F_RANKED_SHARD = 32768  # gm_plan_keyed_shard: md5 shards of the RANKED layout (toot-and-otto)
 GM_F_PLANE_LEVELS = 65536  # PLANES A/B: per-level launches instead of the one-launch backward (k_plane_flow)
+GM_F_RANKED = 131072  # gm_plan: connect four in the RANKED layout (gm_ranked_connect.h) instead of BUCKETED
 KERNEL_FLAGS = (GM_F_WORDS32 | GM_F_RESOLVE_SCALAR | GM_F_SHARD_INORDER | GM_F_WORDS16 | GM_F_BK_EXACT
                 | GM_F_GRAPH | GM_F_LEVEL_MAJOR | GM_F_PLANE_X1 | GM_F_PLANE_ROUND_ROBIN
                 | GM_F_PLANE_LEVEL_SYNC | GM_F_PLANE_NO_RUNS | GM_F_PLANE_LEVELS
@@ -42,7 +43,7 @@ KERNEL_FLAGS = (GM_F_WORDS32 | GM_F_RESOLVE_SCALAR | GM_F_SHARD_INORDER | GM_F_W
 RESOLVE_KERNELS = {1: "k_dense_resolve8p", 2: "k_dense_resolve8c", 3: "k_dense_resolve4p",
                    4: "k_dense_resolve4c", 5: "k_dense_resolve4", 6: "k_dense_resolve",
                    7: "k_dense_resolve16p", 8: "k_plane_resolve", 9: "k_plane_resolve_x2",
-                   10: "k_rk_backward", 11: "k_plane_flow"}
+                   10: "k_rk_backward", 11: "k_plane_flow", 12: "k_c4_backward"}
 PULL_KERNELS = {1: "k_dense_pull_words", 2: "k_dense_pull", 3: "k_plane_reach"}
 GM_MODE_HASHED, GM_MODE_DENSE, GM_MODE_BUCKETED, GM_MODE_PLANES, GM_MODE_RANKED = 0, 1, 2, 3, 4
 # host-staged transport (include/gamesman.h gm_xfer_fn)
@@ -131,7 +132,7 @@ EXPORTS = (
     "gm_ks_begin", "gm_ks_level_size", "gm_ks_expand", "gm_ks_insert",
     "gm_ks_finalize", "gm_ks_counts", "gm_ks_children", "gm_ks_reduce",
     "gm_ks_end", "gm_graph_solve",
-    "gm_tb_info", "gm_tb_index", "gm_solver_export",
+    "gm_tb_info", "gm_tb_index", "gm_ranked_slots", "gm_solver_export",
     "gm_mix64", "gm_solver_export_keyed",
     "gm_last_error", "gm_version",
 )
@@ -192,6 +193,7 @@ def load():
                              c.c_void_p],
         "gm_tb_info": [c.c_int, P(c.c_uint64)],
         "gm_tb_index": [c.c_int, c.c_void_p, c.c_size_t, c.c_void_p],
+        "gm_ranked_slots": [c.c_int, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p],
         "gm_solver_export": [c.c_void_p, c.c_uint32, c.c_uint64, c.c_uint64, c.c_uint32, c.c_void_p,
                              c.c_void_p, c.c_void_p, c.c_uint64, P(c.c_uint64)],
         "gm_mix64": [c.c_void_p, c.c_size_t, c.c_void_p],

@@ -332,7 +332,7 @@ static void census_launch(gm_solver* s, bool generic, const CensusOut& o) {
                            s->stream, s->d, s->pg, (const uint4*)s->ptab, (const uint32_t*)s->pbits, o);
       });
     });
-  } else if (!generic && s->mode == GM_MODE_RANKED) {
+  } else if (!generic && s->mode == GM_MODE_RANKED && s->d.kind != K_CONNECT) {
     const u64 nwords = s->rg.nslots / 64;
     const int grid = (int)std::max<u64>(1, std::min<u64>((nwords + kBlock - 1) / kBlock, (u64)s->grid));
     hipLaunchKernelGGL((k_rk_census<WIT>), dim3(grid), dim3(kBlock), 0, s->stream, s->rg, (const u64*)s->rlv_dev,

@@ -1122,9 +1122,15 @@ static void rank_backward_level(gm_solver* s, hipStream_t st, uint32_t L, const 
 
 // Steps (gm_solver_set_steps): forward level L is step L, backward level L
 // step 2T - 1 - L, as for the other layouts.
+// Connect four (gm_ranked_connect.h) runs the same schedule with its own
+// level launches.
+static void c4_forward_level(gm_solver* s, hipStream_t st, uint32_t L);
+static void c4_backward_level(gm_solver* s, hipStream_t st, uint32_t L);
+static void c4_finish(gm_solver* s, hipStream_t st);
 static int run_ranked(gm_solver* s, gm_result* out) {
   const RankGeom& g = s->rg;
-  const int T = (int)g.T;
+  const bool c4 = s->d.kind == K_CONNECT;
+  const int T = (int)(c4 ? s->kg.T : g.T);
   const int first = (int)s->step_first, stop = s->step_stop ? (int)s->step_stop : 2 * T;
   s->step_first = s->step_stop = 0;
   const bool timing = (s->flags & GM_F_KERNEL_TIMING) && first == 0 && stop == 2 * T;
@@ -1147,12 +1153,14 @@ static int run_ranked(gm_solver* s, gm_result* out) {
   }
   u64 nl_f = 0, nl_b = 0;
   for (int k = std::max(first, 0); k < std::min(stop, T); k++) {
-    rank_forward_level(s, st, (uint32_t)k);
+    if (c4) c4_forward_level(s, st, (uint32_t)k);
+    else rank_forward_level(s, st, (uint32_t)k);
     nl_f += 2;
   }
   HIPCHK(hipEventRecord(ev[1], st));
   for (int k = std::max(first, T); k < stop; k++) {
-    rank_backward_level(s, st, (uint32_t)(2 * T - 1 - k));
+    if (c4) c4_backward_level(s, st, (uint32_t)(2 * T - 1 - k));
+    else rank_backward_level(s, st, (uint32_t)(2 * T - 1 - k));
     nl_b++;
   }
   HIPCHK(hipGetLastError());
@@ -1163,7 +1171,8 @@ static int run_ranked(gm_solver* s, gm_result* out) {
     out->word_bits = 8;
     return GM_PARTIAL;
   }
-  hipLaunchKernelGGL(k_rk_finish, dim3(1), dim3(1024), 0, st, g, s->rlvstart[0], s->st, (const BlockCount*)s->bcount);
+  if (c4) c4_finish(s, st);
+  else hipLaunchKernelGGL(k_rk_finish, dim3(1), dim3(1024), 0, st, g, s->rlvstart[0], s->st, (const BlockCount*)s->bcount);
   HIPCHK(hipGetLastError());
   u64 red[5];
   HIPCHK(hipMemcpyAsync(red, s->st->red, sizeof red, hipMemcpyDeviceToHost, st));
@@ -1187,7 +1196,7 @@ static int run_ranked(gm_solver* s, gm_result* out) {
   out->levels = (uint32_t)T;
   out->max_level_width = 0;
   out->word_bits = 8;
-  out->kernels = RK_RANKED;
+  out->kernels = c4 ? RK_RANKED_CONNECT : RK_RANKED;
   const uint32_t word = red[3] ? (uint32_t)(red[3] - 1) : NO_WORD;
   out->root_word = word;
   if (red[4]) return fail(GM_ECORRUPT, "solve failed:%s", err_text((uint32_t)red[4]).c_str());

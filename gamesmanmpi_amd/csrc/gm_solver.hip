@@ -20,6 +20,7 @@
 //                        run_dense (no kernels)
 //   gm_plane_run.h       PLANES host path and its late kernels
 //   gm_ranked.h gm_ranked_shard.h  RANKED kernels and host path, its md5 shards
+//   gm_ranked_connect.h            RANKED kernels and host path of connect four
 //   gm_bucketed_run.h    BUCKETED host path (no kernels)
 //   gm_bucketed_shard.h  md5-sharded BUCKETED levels
 //   (here)               the C-ABI over the layouts: plans, creation, solves
@@ -791,6 +792,32 @@ struct RankGeom {
   u64* pbits;              // [nslots / 512] per board: primitive
   u64 le[7];               // bits j < 64 with popcount(j) <= c
 };
+// RANKED layout geometry of connect four (gm_ranked_connect.h): a height
+// vector's block is its 2^L stack patterns (bit = 1: an X piece), no hands.
+// Blocks are named by their ORDINAL inside their level (all blocks of a level
+// have 2^L slots): block j of level L starts at slot lvstart[L] + (j << L),
+// a 64-bit sum -- levels of 6x5 and 5x6 pass 2^32 slots.
+struct C4Geom {
+  uint32_t C, H, R, A;     // columns, rows, height radix H + 1, cells
+  uint32_t T;              // levels (pieces 0 .. A)
+  uint32_t stride[kRankMaxCols];  // hvcode stride of column x: R^x
+  uint32_t spread;         // C > H: a column's stack reaches its cells by one multiply (mul, msk)
+  uint32_t mul, msk;       // sum of 2^((C-1) y), sum of 2^(C y), y < H
+  u64 nslots;
+  uint8_t* words;          // [nslots] the board pass' primitive value / UNDECIDED, then the solved word
+  uint32_t* reach;         // [nslots / 32] reached
+  uint32_t* expd;          // [nslots / 32] reached and not primitive
+  u64* pbits;              // [nslots / 64] primitive (or no position: unbalanced colours)
+  const u64* lvstart;      // [T + 1] per level: first slot (512-aligned)
+  const uint32_t* lvoff;   // [T + 1] per level: first entry of its block list
+  const uint32_t* ord;     // [R^C] hvcode -> ordinal of its block in its level
+  const uint32_t* lvph;    // per block entry: heights packed 4 bits per column
+  const uint32_t* lvch;    // per block entry, kRankMaxCols u32: child block x's ordinal in level L + 1
+                           // (0xFFFFFFFF: column x full)
+  const uint32_t* lvpa;    // per block entry, kRankMaxCols u32: parent block x's ordinal in level L - 1
+                           // (0xFFFFFFFF: column x empty)
+  u64 eq[7];               // bits j < 64 with popcount(j) == c
+};
 
 enum DenseResolveKind : uint32_t {
   RK_NONE = 0,
@@ -805,6 +832,7 @@ enum DenseResolveKind : uint32_t {
   RK_PLANE_X2 = 9,   // k_plane_resolve_x2: two planes per half-wave, packed 16-bit lanes
   RK_RANKED = 10,    // k_rk_backward: RANKED layout (gm_ranked.h)
   RK_PLANE_FLOW = 11,  // k_plane_flow: the one-launch PLANES backward (gm_plane.h)
+  RK_RANKED_CONNECT = 12,  // k_c4_backward: RANKED layout of connect four (gm_ranked_connect.h)
 };
 enum DensePullKind : uint32_t { PK_NONE = 0, PK_WORDS = 1, PK_LANE = 2, PK_PLANE = 3 };
 
@@ -942,6 +970,10 @@ struct gm_solver {
   std::vector<uint32_t> rlvoff;        // per level: first entry of its block list
   std::vector<u64> rlvstart, rlvitems;  // per level: first slot, slots
   u64* rlv_dev = nullptr;              // device: rlvstart then rlvoff (RankEnum's lvt)
+  // RANKED, connect four (gm_ranked_connect.h): rlvoff / rlvstart / rlvitems as
+  // above; the index tables live in an allocation of the solver's own
+  C4Geom kg{};
+  void* c4_dev = nullptr;
   u64* cen_dev = nullptr;              // device: gm_solver_census' counts, maxima and witnesses (gm_census.h)
   // gm_solver_export (gm_export.h): block offsets and totals of a call (device,
   // grown on demand); for toot tables of the keyed layouts the level tables
@@ -1274,6 +1306,7 @@ __global__ __launch_bounds__(1024) void k_fill_red(DevState* st, const BlockCoun
 #include "gm_plane_run.h"
 #include "gm_ranked.h"
 #include "gm_ranked_shard.h"
+#include "gm_ranked_connect.h"
 #include "gm_bucketed_run.h"
 #include "gm_bucketed_shard.h"
 
@@ -1372,6 +1405,14 @@ int gm_plan(int game, uint64_t positions, uint32_t flags, uint64_t max_table_byt
     out->max_levels = (uint32_t)d->max_levels;
     out->scratch_bytes = scratch_bytes_for(d->max_levels);
   }
+  if ((flags & GM_F_RANKED) && d->kind == K_CONNECT) {  // on request: connect four at computed indices
+    if (const char* why = c4_rank_why(d)) return fail(GM_EINVAL, "%s", why);
+    bool fits = false;
+    int rc = plan_c4_ranked(d, max_table_bytes, out, &fits);
+    if (rc) return rc;
+    if (!fits) return fail(GM_EFULL, "ranked table needs %llu bytes", (unsigned long long)out->table_bytes);
+    return 0;
+  }
   if (rank_wanted(d, flags)) {  // toot-and-otto: positions at computed indices (gm_ranked.h)
     bool fits = false;
     int rc = plan_ranked(d, max_table_bytes, out, &fits);
@@ -1419,6 +1460,8 @@ int gm_plan_keyed_shard(int game, int rank, int world, uint64_t positions, uint3
   if (flags & GM_F_RANKED_SHARD) {  // the RANKED index space, md5-owned slots (gm_ranked_shard.h)
     memset(out, 0, sizeof *out);
     if (d->bsym) return fail(GM_EINVAL, "board_symmetry=1 has no ranked layout: the RANKED index has no representative form");
+    if (d->kind == K_CONNECT)
+      return fail(GM_EINVAL, "md5 shards of the RANKED layout serve toot-and-otto boards only (connect four: one GPU)");
     return plan_ranked_shard(d, world, max_table_bytes, out);
   }
   if (!bk_ok(d) || (flags & GM_F_HASH_TABLE))
@@ -1468,7 +1511,12 @@ int gm_solver_create_shard(int game, int rank, int world, const gm_buffers* buf,
       return fail(GM_EINVAL, "ranked md5 shards are planned with GM_F_RANKED_SHARD (gm_plan_keyed_shard)");
     if (world > 8 || rank < 0 || rank >= world) return fail(GM_EINVAL, "bad ranked shard %d/%d (2..8 ranks)", rank, world);
     if (d->bsym) return fail(GM_EINVAL, "board_symmetry=1 has no ranked layout: the RANKED index has no representative form");
-    if (!rank_ok(d)) return fail(GM_EINVAL, "game has no ranked layout");
+    if (d->kind == K_CONNECT) {
+      if (world != 1) return fail(GM_EINVAL, "the RANKED layout of connect four runs on one GPU");
+      if (const char* why = c4_rank_why(d)) return fail(GM_EINVAL, "%s", why);
+    } else if (!rank_ok(d)) {
+      return fail(GM_EINVAL, "game has no ranked layout");
+    }
   } else if (buf->mode == GM_MODE_BUCKETED) {
     if (world < 1 || rank < 0 || rank >= world) return fail(GM_EINVAL, "bad shard %d/%d", rank, world);
     if (world > 8) return fail(GM_EINVAL, "md5-sharded bucketed levels support up to 8 ranks");
@@ -1528,7 +1576,7 @@ int gm_solver_create_shard(int game, int rank, int world, const gm_buffers* buf,
     case GM_MODE_DENSE: rc = dense_setup(s, buf); break;
     case GM_MODE_BUCKETED: bk_setup(s, buf); break;
     case GM_MODE_PLANES: rc = plane_setup(s, buf); break;
-    case GM_MODE_RANKED: rc = rank_setup(s, buf); break;
+    case GM_MODE_RANKED: rc = d->kind == K_CONNECT ? c4_setup(s, buf) : rank_setup(s, buf); break;
     default: break;  // HASHED: the common fields are all of it
   }
   if (rc) {  // (fail()'s message stands: gm_solver_destroy sets none)
@@ -1629,6 +1677,7 @@ void gm_solver_destroy(gm_solver* s) {
   if (s->errg) (void)hipFree(s->errg);
   if (s->xdev) (void)hipFree(s->xdev);
   if (s->rlv_dev) (void)hipFree(s->rlv_dev);
+  if (s->c4_dev) (void)hipFree(s->c4_dev);
   if (s->cen_dev) (void)hipFree(s->cen_dev);
   if (s->exp_dev) (void)hipFree(s->exp_dev);
   if (s->xgeo_dev) (void)hipFree(s->xgeo_dev);
@@ -1795,6 +1844,36 @@ int gm_tb_index(int game, const uint64_t* keys, size_t n, uint64_t* index) {
     uint32_t L;
     index[i] = rk_slot_of(rs.g, keys[i], &slot, &L) ? slot : GM_NO_INDEX;
   }
+  return 0;
+}
+
+int gm_ranked_slots(int game, const uint64_t* keys, size_t n, uint64_t* slots, uint32_t* levels) {
+  const Desc* d = get_game(game);
+  if (!d || (n && (!keys || !slots || !levels))) return fail(GM_EINVAL, "bad argument");
+  if (d->bsym) return fail(GM_EINVAL, "board_symmetry=1 has no ranked layout: the RANKED index has no representative form");
+  auto each = [&](auto&& slot_of) {
+    for (size_t i = 0; i < n; i++) {
+      u64 slot;
+      uint32_t L;
+      const bool ok = slot_of(keys[i], &slot, &L);
+      slots[i] = ok ? slot : GM_NO_INDEX;
+      levels[i] = ok ? L : 0xFFFFFFFFu;
+    }
+  };
+  if (d->kind == K_CONNECT) {
+    if (const char* why = c4_rank_why(d)) return fail(GM_EINVAL, "%s", why);
+    C4Shape cs;
+    c4_shape(d, &cs);
+    c4_host_geom(&cs);
+    each([&](u64 key, u64* slot, uint32_t* L) { return c4_slot_of(cs.g, key, slot, L); });
+    return 0;
+  }
+  if (!rank_ok(d)) return fail(GM_EINVAL, "game has no ranked layout (toot-and-otto and connect four boards have one)");
+  RankShape rs;
+  const int rc = rank_shape(d, &rs);
+  if (rc) return rc;
+  rs.g.base = rs.base.data();
+  each([&](u64 key, u64* slot, uint32_t* L) { return rk_slot_of(rs.g, key, slot, L); });
   return 0;
 }
 

@@ -66,6 +66,11 @@ struct RankWords {
   __device__ __forceinline__ uint32_t operator()(const Desc&, u64 key) const { return rk_word(g, key); }
 };
 
+struct C4Words {  // RANKED, connect four (gm_ranked_connect.h)
+  C4Geom g;
+  __device__ __forceinline__ uint32_t operator()(const Desc&, u64 key) const { return c4_word(g, key); }
+};
+
 // ---------------------------------------------------------------------------
 // position enumerators and pair sources, per layout
 // ---------------------------------------------------------------------------
@@ -243,6 +248,36 @@ struct RankPairs : RankEnum {
   }
 };
 
+struct C4Enum {  // RANKED, connect four: one 64-slot word of the reach bitmap per item; place: the slot
+  static constexpr bool kOnePerItem = false;
+  C4Geom g;
+  __device__ __forceinline__ u64 items() const { return g.nslots / 64; }
+  template <class N, class F>
+  __device__ __forceinline__ void each(const Desc&, u64 wi, N&& n, F&& f) const {
+    u64 m = reinterpret_cast<const u64*>(g.reach)[wi];
+    if (!m) return;
+    const u64 s0 = wi << 6;  // (levels start 512-aligned: a word belongs to one level)
+    uint32_t L = 0;
+    while (L + 1 < g.T && g.lvstart[L + 1] <= s0) L++;
+    n((uint32_t)__builtin_popcountll(m));
+    for (; m; m &= m - 1) {
+      const u64 slot = s0 + (u64)__builtin_ctzll(m);
+      f(c4_slot_key(g, L, slot), slot);
+    }
+  }
+  template <class F>
+  __device__ __forceinline__ void visit(const Desc& d, u64 i, F&& f) const {
+    visit_keys(*this, d, i, f);
+  }
+};
+struct C4Pairs : C4Enum {
+  __device__ __forceinline__ uint32_t word(u64, u64 slot) const { return g.words[slot]; }
+  template <class F>
+  __device__ __forceinline__ void visit(const Desc& d, u64 i, F&& f) const {
+    visit_pairs(*this, d, i, f);
+  }
+};
+
 // ---------------------------------------------------------------------------
 // host: the solver's layout as each of the three views
 // ---------------------------------------------------------------------------
@@ -260,6 +295,8 @@ static void moves_words_dispatch(gm_solver* s, F&& f) {
     plane_form_dispatch(s, [&](auto WB, auto) {
       f(PlaneWords<decltype(WB)::value>{s->pg, (const void*)s->ptab, (const uint32_t*)s->pbits});
     });
+  else if (s->mode == GM_MODE_RANKED && s->d.kind == K_CONNECT)
+    f(C4Words{s->kg});
   else if (s->mode == GM_MODE_RANKED)
     f(RankWords{s->rg});
   else if (s->mode == GM_MODE_DENSE)
@@ -274,6 +311,8 @@ template <class F>
 static void moves_enum_dispatch(gm_solver* s, F&& f) {
   if (s->mode == GM_MODE_PLANES)
     plane_no_dispatch(s->pg.no, [&](auto NO) { f(PlaneEnum<decltype(NO)::value>{s->pg, (const uint32_t*)s->pbits}); });
+  else if (s->mode == GM_MODE_RANKED && s->d.kind == K_CONNECT)
+    f(C4Enum{s->kg});
   else if (s->mode == GM_MODE_RANKED)
     f(RankEnum{s->rg, (const u64*)s->rlv_dev, s->rg.T, s->rg.nslots / 64});
   else if (s->mode == GM_MODE_DENSE)
@@ -296,6 +335,8 @@ static void pairs_of(gm_solver* s, const PlaneEnum<NO>& en, F&& f) {
 }
 template <class F>
 static void pairs_of(gm_solver*, const RankEnum& en, F&& f) { f(RankPairs{en}); }
+template <class F>
+static void pairs_of(gm_solver*, const C4Enum& en, F&& f) { f(C4Pairs{en}); }
 template <class F>
 static void pairs_dispatch(gm_solver* s, F&& f) {
   moves_enum_dispatch(s, [&](auto en) { pairs_of(s, en, f); });

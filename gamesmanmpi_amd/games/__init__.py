@@ -184,6 +184,17 @@ class GameSpec:
                                            len(keys), out.ctypes.data))
         return out
 
+    def ranked_slots(self, keys):
+        """(slot uint64[n], level uint32[n]) of each key in the game's RANKED
+        layout (toot-and-otto, connect four); GM_NO_INDEX and 0xFFFFFFFF for
+        a key that is no position.  Host arithmetic: no GPU, no table."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        slots = np.zeros(len(keys), np.uint64)
+        levels = np.zeros(len(keys), np.uint32)
+        _lib.check(_lib.load().gm_ranked_slots(self.id, keys.ctypes.data, len(keys),
+                                               slots.ctypes.data, levels.ctypes.data))
+        return slots, levels
+
     def owners_host(self, keys, world_size):
         """GameState.get_hash(world_size) (src/game_state.py:22-30)."""
         keys = np.ascontiguousarray(keys, dtype=np.uint64)

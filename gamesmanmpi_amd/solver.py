@@ -55,7 +55,10 @@ class Solver:
         advances one level; else the keyed hash table), "planes" (sum games
         whose first two heaps hold 32 values: natural rank order,
         gm_plane.h), "dense" (the level-major dense table), "ranked"
-        (toot-and-otto positions at computed indices, gm_ranked.h),
+        (positions at computed indices: toot-and-otto, gm_ranked.h, which
+        "auto" picks too, and connect four, gm_ranked_connect.h, on request
+        only -- boards up to 8 columns, 7 rows and 2^36 slots, 6x5 included,
+        one GPU),
         "bucketed" or "hashed" (the open-addressing hash table).
         flags: kernel-family flags (_lib.GM_F_WORDS32 / GM_F_RESOLVE_SCALAR /
         GM_F_SHARD_INORDER, A/B runs), fixed for this solver's lifetime.
@@ -106,7 +109,8 @@ class Solver:
         plan = _lib.gm_plan_t()
         flags = self.flags | {"hashed": _lib.GM_F_FORCE_HASHED | _lib.GM_F_HASH_TABLE,
                               "bucketed": _lib.GM_F_FORCE_HASHED,
-                              "dense": _lib.GM_F_LEVEL_MAJOR}.get(self._planned_layout, 0)
+                              "dense": _lib.GM_F_LEVEL_MAJOR,
+                              "ranked": _lib.GM_F_RANKED}.get(self._planned_layout, 0)
         if self.world > 1 and self.layout in ("bucketed", "ranked"):
             # an md5 shard of bucketed levels (`positions` bounds this
             # shard), or of the RANKED index space (toot-and-otto)
@@ -130,8 +134,8 @@ class Solver:
             raise ValueError("%r has no planes layout (heaps 0 and 1 of 32 "
                              "values), or it does not fit" % (self.spec,))
         if self.layout == "ranked" and plan.mode != _lib.GM_MODE_RANKED:
-            raise ValueError("%r has no ranked layout (toot-and-otto boards), or it "
-                             "does not fit" % (self.spec,))
+            raise ValueError("%r has no ranked layout (toot-and-otto and connect four "
+                             "boards), or it does not fit" % (self.spec,))
         if self.layout == "bucketed" and plan.mode != _lib.GM_MODE_BUCKETED:
             raise ValueError("%r: bucketed levels need every move to advance "
                              "one level" % (self.spec,))

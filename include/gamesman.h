@@ -165,6 +165,12 @@ typedef struct gm_buffers {
                                   pairs) instead of the one-launch backward
                                   (k_plane_flow; A/B, and the schedule of
                                   partial / resumed solves) */
+#define GM_F_RANKED 131072u /* gm_plan: connect four at computed indices, the
+                                  RANKED layout (gm_ranked_connect.h), instead
+                                  of BUCKETED levels; GM_EINVAL says why a
+                                  board has none.  Toot-and-otto plans RANKED
+                                  by itself, with or without the flag; other
+                                  games ignore it */
 #define GM_F_GRAPH 256u      /* dense one-table full solves: capture the
                                   forward and backward launches as HIP graphs
                                   on the first solve, replay them after
@@ -403,6 +409,13 @@ int gm_tb_info(int game, uint64_t *index_space);
 /* index[i] = tablebase index of keys[i]; GM_NO_INDEX for a key that is no
  * position of the game */
 int gm_tb_index(int game, const uint64_t *keys, size_t n, uint64_t *index);
+/* slots[i], levels[i] = the RANKED layout's slot and level (pieces on the
+ * board) of keys[i]; GM_NO_INDEX and 0xFFFFFFFF for a key that is no position
+ * of the game.  For the games with a RANKED layout: toot_and_otto_bitstring
+ * (as gm_tb_index) and connect_four (GM_F_RANKED: height vectors in code
+ * order, blocks of 2^L slots, levels padded to 512), GM_EINVAL otherwise.
+ * Host only: no GPU and no table needed. */
+int gm_ranked_slots(int game, const uint64_t *keys, size_t n, uint64_t *slots, uint32_t *levels);
 /* Indexes [first, first + count) of a finished solve as tablebase sections,
  * written on the device: bit i of bits_dev (count / 64 u64) = index first + i
  * is reached, block_counts_dev (count / GM_TB_BLOCK u32) = reached indexes
