@@ -50,7 +50,8 @@ GM_MODE_HASHED, GM_MODE_DENSE, GM_MODE_BUCKETED, GM_MODE_PLANES, GM_MODE_RANKED 
 GM_XFER_SENDRECV, GM_XFER_ALLGATHER = 0, 1
 XFER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
                            ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int)
-MODE_NAMES = {0: "hashed", 1: "dense", 2: "bucketed", 3: "planes", 4: "ranked"}
+GM_MODE_FILE = 5  # gm_solver_open_table: a saved tablebase's bytes, read in place
+MODE_NAMES = {0: "hashed", 1: "dense", 2: "bucketed", 3: "planes", 4: "ranked", 5: "file"}
 GM_MAXCHILD = 32
 GM_COMM_ID_BYTES = 128
 GM_NO_WORD = 0xFFFFFFFF
@@ -133,7 +134,7 @@ EXPORTS = (
     "gm_ks_finalize", "gm_ks_counts", "gm_ks_children", "gm_ks_reduce",
     "gm_ks_end", "gm_graph_solve",
     "gm_tb_info", "gm_tb_index", "gm_ranked_slots", "gm_solver_export",
-    "gm_mix64", "gm_solver_export_keyed",
+    "gm_mix64", "gm_solver_export_keyed", "gm_table_check", "gm_solver_open_table",
     "gm_last_error", "gm_version",
 )
 
@@ -199,6 +200,9 @@ def load():
         "gm_mix64": [c.c_void_p, c.c_size_t, c.c_void_p],
         "gm_solver_export_keyed": [c.c_void_p, c.c_uint32, c.c_uint32, c.c_uint32, c.c_void_p, c.c_void_p,
                                    c.c_void_p, c.c_void_p, c.c_uint64, c.c_void_p],
+        "gm_table_check": [c.c_int, c.c_char_p, c.c_uint64, c.c_uint64, c.c_void_p],
+        "gm_solver_open_table": [c.c_int, c.c_void_p, c.c_uint64, c.c_void_p, c.c_uint64, c.c_void_p,
+                                 P(c.c_void_p)],
         "gm_solve":[c.c_int, c.c_uint64, c.c_int, P(gm_buffers),
                      P(gm_result)],
         "gm_plan_multi": [c.c_int, c.c_int, c.c_uint64, c.c_uint32, c.c_uint64, P(gm_plan_t)],

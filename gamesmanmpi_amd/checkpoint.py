@@ -140,6 +140,8 @@ def _stream_in(t, path, torch):
 def save(solver, directory, step):
     """Write `solver`'s buffers after step `step` (its last solve_steps call
     stopped there) to `directory`."""
+    if getattr(solver, "layout", None) == "file":  # (table.OpenTable)
+        raise _lib.GmError(_lib.GM_EINVAL, "checkpoint: an opened tablebase file is read, never solved")
     if solver.world != 1:
         raise ValueError("checkpoints cover one-GPU solves")
     directory = directory.rstrip("/")

@@ -42,7 +42,7 @@ constexpr uint32_t kTkBucketCap = 1024;  // positions of one bucket (k_tk_sort's
 // device scratch (gm_solver::exp_dev): [EXP_WORDS | TK_WORDS | part[nparts] | counts u32[2^b]]
 enum { TK_OR = 0, TK_BAD = 1, TK_MAXBUCKET = 2, TK_WORDS = 4 };
 
-__device__ __forceinline__ u64 tk_bucket(u64 key, uint32_t b) { return b ? mix64(key) >> (64u - b) : 0ull; }
+// (tk_bucket: gm_table_file.h, which reads the buckets back)
 
 // ---------------------------------------------------------------------------
 // the pair source (gm_table.h) that reads nothing in place: the deliberately

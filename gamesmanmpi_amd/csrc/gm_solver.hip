@@ -835,6 +835,8 @@ enum DenseResolveKind : uint32_t {
   RK_RANKED_CONNECT = 12,  // k_c4_backward: RANKED layout of connect four (gm_ranked_connect.h)
 };
 enum DensePullKind : uint32_t { PK_NONE = 0, PK_WORDS = 1, PK_LANE = 2, PK_PLANE = 3 };
+struct TbGeom;  // an opened tablebase file's sections (gm_table_file.h)
+struct TkGeom;
 
 struct gm_solver {
   Desc d;
@@ -990,6 +992,11 @@ struct gm_solver {
   uint32_t *rko_cnt = nullptr, *rko_toff = nullptr;
   u64* rko_tot = nullptr;
   std::vector<u64> rko_tile0, rko_tot_h;
+  // GM_MODE_FILE (gm_table_file.h): the sections of the opened image, one of
+  // the two by the file's format (1 gmtb, 2 gmtk), and its word bytes
+  TbGeom* tb = nullptr;
+  TkGeom* tk = nullptr;
+  uint32_t tf_format = 0, tf_wb = 0;
 };
 
 static const int kBlock = 256;
@@ -1309,6 +1316,7 @@ __global__ __launch_bounds__(1024) void k_fill_red(DevState* st, const BlockCoun
 #include "gm_ranked_connect.h"
 #include "gm_bucketed_run.h"
 #include "gm_bucketed_shard.h"
+#include "gm_table_file.h"
 
 int gm_rk_shard_stats(gm_solver* s, uint64_t out[2]) {
   if (!s || !out) return fail(GM_EINVAL, "bad argument");
@@ -1638,8 +1646,15 @@ int gm_solver_set_transport(gm_solver* s, gm_xfer_fn fn, void* ctx) {
   return 0;
 }
 
+// an opened tablebase file (gm_solver_open_table) is read, never solved
+static int table_file_refuses(const char* what) {
+  return fail(GM_EINVAL, "%s: the solver is an opened tablebase file (gm_solver_open_table): it serves the readers "
+                         "only -- no solve, no steps, no flags", what);
+}
+
 int gm_solver_set_steps(gm_solver* s, uint32_t first, uint32_t stop) {
   if (!s) return fail(GM_EINVAL, "bad argument");
+  if (s->mode == GM_MODE_FILE) return table_file_refuses("gm_solver_set_steps");
   const uint32_t n = 2u * (uint32_t)s->d.max_levels;
   if (s->world > 1) return fail(GM_EINVAL, "stop/resume drives one-GPU solves only");
   if (first > n || (stop && (stop <= first || stop > n))) return fail(GM_EINVAL, "bad step range [%u, %u) of %u", first, stop, n);
@@ -1650,6 +1665,7 @@ int gm_solver_set_steps(gm_solver* s, uint32_t first, uint32_t stop) {
 
 int gm_solver_set_flags(gm_solver* s, uint32_t flags) {
   if (!s) return fail(GM_EINVAL, "null solver");
+  if (s->mode == GM_MODE_FILE) return table_file_refuses("gm_solver_set_flags");
   if ((flags & ~GM_F_KERNEL_TIMING) != (s->flags & ~GM_F_KERNEL_TIMING))
     return fail(GM_EINVAL, "only GM_F_KERNEL_TIMING changes after creation: the kernel families and word width "
                            "are fixed by the flags the solver was planned and created with");
@@ -1681,6 +1697,8 @@ void gm_solver_destroy(gm_solver* s) {
   if (s->cen_dev) (void)hipFree(s->cen_dev);
   if (s->exp_dev) (void)hipFree(s->exp_dev);
   if (s->xgeo_dev) (void)hipFree(s->xgeo_dev);
+  delete s->tb;
+  delete s->tk;
   if (s->own_stream) (void)hipStreamDestroy(s->stream);
   delete s;
 }
@@ -1725,6 +1743,7 @@ static int solve_by_mode(const std::vector<gm_solver*>& ss, gm_result* out) {
 
 int gm_solver_solve(gm_solver* s, gm_result* out) {
   if (!s || !out) return fail(GM_EINVAL, "bad argument");
+  if (s->mode == GM_MODE_FILE) return table_file_refuses("gm_solver_solve");
   s->solved = false;
   memset(out, 0, sizeof *out);
   const int rc = solve_by_mode({s}, out);
@@ -1738,6 +1757,8 @@ int gm_solve_group(gm_solver** shards, int n, gm_result* out) {
   std::vector<gm_solver*> ss(shards, shards + n);
   for (gm_solver* s : ss)
     if (!s) return fail(GM_EINVAL, "null shard");
+  for (gm_solver* s : ss)
+    if (s->mode == GM_MODE_FILE) return table_file_refuses("gm_solve_group");
   for (gm_solver* s : ss) s->solved = false;
   // a group's BUCKETED shards take the sharded loop whatever their world, and
   // keyed tables meet the dense loop's group checks; the rest is one dispatch
@@ -1835,7 +1856,7 @@ int gm_tb_index(int game, const uint64_t* keys, size_t n, uint64_t* index) {
   if (rc) return rc;
   if (d->kind == K_SUM) {
     const u64 total = tb_sum_total(d);
-    for (size_t i = 0; i < n; i++) index[i] = keys[i] < total ? keys[i] : GM_NO_INDEX;
+    for (size_t i = 0; i < n; i++) index[i] = tb_sum_index(total, keys[i]);
     return 0;
   }
   rs.g.base = rs.base.data();  // (the host's copy: rk_slot_of reads nothing else through a pointer)
@@ -1930,6 +1951,30 @@ int gm_solver_positions(gm_solver* s, uint64_t* keys_dev, uint64_t cap, uint64_t
 int gm_solver_checksum(gm_solver* s, uint64_t out[6]) {
   if (!s || !out) return fail(GM_EINVAL, "bad argument");
   return checksum_run(s, out);
+}
+
+#define GM_TABLE_FILE_HOST 1
+#include "gm_table_file.h"
+
+int gm_table_check(int game, const void* header, uint64_t header_bytes, uint64_t file_bytes, uint64_t out[12]) {
+  const Desc* d = get_game(game);
+  if (!d || !header || !out) return fail(GM_EINVAL, "bad argument");
+  TfInfo fi;
+  const int rc = table_check(d, (const uint8_t*)header, header_bytes, file_bytes, &fi);
+  if (rc) return rc;
+  const uint64_t v[12] = {fi.format,    fi.positions, fi.wb,  fi.kb,        fi.b,
+                          fi.space,     fi.off0,      fi.off1, fi.words_off,
+                          (scratch_bytes_for(d->max_levels) + 255) / 256 * 256 + fi.index_bytes, fi.index_bytes, 0};
+  memcpy(out, v, sizeof v);
+  return 0;
+}
+
+int gm_solver_open_table(int game, const void* image_dev, uint64_t bytes, void* scratch_dev, uint64_t scratch_bytes,
+                         void* stream, gm_solver** out) {
+  const Desc* d = get_game(game);
+  if (!d || !image_dev || !scratch_dev || !out) return fail(GM_EINVAL, "bad argument");
+  *out = nullptr;
+  return table_open(d, image_dev, bytes, scratch_dev, scratch_bytes, stream, out);
 }
 
 // gm_solve keeps its solver per game id until the next gm_solve of that game

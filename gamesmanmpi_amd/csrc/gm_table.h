@@ -288,6 +288,13 @@ static u64 bk_positions(const gm_solver* s) {
   return tot;
 }
 
+// f(word bytes) of an opened gmtb (1 for a gmtk, whose views read the width at run time)
+template <class F>
+static void tf_word_bytes_dispatch(gm_solver* s, F&& f) {
+  if (s->tf_format == 2 || s->tf_wb == 1) f(std::integral_constant<int, 1>{});
+  else if (s->tf_wb == 2) f(std::integral_constant<int, 2>{});
+  else f(std::integral_constant<int, 4>{});
+}
 // f(word functor) for the solver's layout
 template <class F>
 static void moves_words_dispatch(gm_solver* s, F&& f) {
@@ -303,6 +310,11 @@ static void moves_words_dispatch(gm_solver* s, F&& f) {
     f(DenseWords{s->view, s->words, s->bits, s->wbits()});
   else if (s->mode == GM_MODE_BUCKETED)
     f(BkWords{s->bkK, s->bkW, s->bkL, s->d.max_levels, s->meta});
+  else if (s->mode == GM_MODE_FILE)  // an opened tablebase file (gm_table_file.h)
+    tf_word_bytes_dispatch(s, [&](auto WB) {
+      if (s->tf_format == 2) f(TkWords{*s->tk});
+      else f(TbWords<decltype(WB)::value>{*s->tb});
+    });
   else
     f(HashedWords{s->tab, s->mask});
 }
@@ -319,6 +331,10 @@ static void moves_enum_dispatch(gm_solver* s, F&& f) {
     f(DenseEnum{s->view, s->bits, (u64)s->d.max_levels});
   else if (s->mode == GM_MODE_BUCKETED)
     f(FlatEnum{s->bkK, bk_positions(s)});
+  else if (s->mode == GM_MODE_FILE && s->tf_format == 2)
+    f(TkEnum{*s->tk});
+  else if (s->mode == GM_MODE_FILE)
+    f(TbEnum{*s->tb});
   else
     f(HashedEnum{s->lv, s->lcap, s->st});
 }
@@ -337,6 +353,12 @@ template <class F>
 static void pairs_of(gm_solver*, const RankEnum& en, F&& f) { f(RankPairs{en}); }
 template <class F>
 static void pairs_of(gm_solver*, const C4Enum& en, F&& f) { f(C4Pairs{en}); }
+template <class F>
+static void pairs_of(gm_solver*, const TkEnum& en, F&& f) { f(TkPairs{en}); }
+template <class F>
+static void pairs_of(gm_solver* s, const TbEnum& en, F&& f) {
+  tf_word_bytes_dispatch(s, [&](auto WB) { f(TbPairs<decltype(WB)::value>{en}); });
+}
 template <class F>
 static void pairs_dispatch(gm_solver* s, F&& f) {
   moves_enum_dispatch(s, [&](auto en) { pairs_of(s, en, f); });
@@ -418,6 +440,8 @@ static int positions_run(gm_solver* s, uint64_t* keys_dev, uint64_t cap, uint64_
   u64 cur[2] = {0, 0};
   if (s->mode == GM_MODE_BUCKETED) {
     cur[0] = bk_positions(s);
+  } else if (s->mode == GM_MODE_FILE) {
+    cur[0] = s->tf_format == 2 ? s->tk->positions : s->tb->positions;  // (the header's, checked at open)
   } else {
     HIPCHK(hipStreamSynchronize(s->stream));
     HIPCHK(hipMemcpy(cur, s->st, sizeof cur, hipMemcpyDeviceToHost));  // cursor_front, cursor_back

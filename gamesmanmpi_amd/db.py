@@ -48,6 +48,16 @@ numpy writer write_keyed_tablebase and its reader KeyedTablebase are below):
 truncated keys grouped by hash bucket and sorted inside a bucket, one compact
 word per key.  `-sd DIR --tablebase` and `--to-tablebase` write it for those
 games, and SolutionDB opens it the same way.
+
+    python -m gamesmanmpi_amd.db DIR --game GAME_FILE --gpu [--audit | --census | --moves] [POSITION ...]
+
+opens the directory's tablebase file on the GPU instead
+(Solver.open_tablebase, gm_solver_open_table): positions
+and --moves are answered from the image on the device, --census prints the
+by-level table and the longest lines too (the launcher's --census output),
+and --audit re-derives every stored word from its children's, printing up to
+64 mismatching positions, exit status 1 on a mismatch.  Without --gpu nothing
+changes and no GPU is touched.
 """
 import argparse
 import ast
@@ -658,6 +668,82 @@ def convert_to_tablebase(root, spec):
     return path
 
 
+def open_on_gpu(db, spec=None, device=None):
+    """The tablebase file of SolutionDB `db` opened on the GPU
+    (Solver.open_tablebase), under the table's own game and params (a
+    symmetric solve's are its key map), else `spec`."""
+    if getattr(db, "tablebase", None) is None:
+        raise ValueError("--gpu opens a tablebase (solution.gmtb / solution.gmtk); this directory holds "
+                         "solution.npz files (convert them with --to-tablebase)")
+    from .games import GameSpec
+    from .solver import Solver
+    if "game" in db.meta:
+        spec = GameSpec(db.meta["game"], db.meta.get("params", ""))
+    if spec is None:
+        raise ValueError("a tablebase needs the game's GameSpec")
+    return Solver.open_tablebase(spec, db.tablebase.path, device=device)
+
+
+def plain_position(pos):
+    """A position as the queries above spell it: nested tuples on one line
+    (GameSpec.pos_of gives board games as numpy arrays)."""
+    if hasattr(pos, "tolist"):
+        pos = pos.tolist()
+    return tuple(plain_position(p) for p in pos) if isinstance(pos, (list, tuple)) else pos
+
+
+def gpu_main(args, db, mod, spec):
+    """main() with --gpu: the same questions answered from the file's image
+    on the device."""
+    from . import _lib
+    try:
+        t = open_on_gpu(db, spec)
+    except (ValueError, _lib.GmError) as e:
+        raise SystemExit("--gpu: %s" % e)
+    spec = t.spec
+    if args.audit:
+        a = t.audit(64)
+        print("audit: %d positions, %d edges, %d mismatches" % (a["positions"], a["edges"], a["mismatches"]))
+        for k in a["bad_keys"].tolist():
+            print("  mismatch at %s" % (plain_position(spec.pos_of(k)),))
+        return 1 if a["mismatches"] else 0
+    if args.census:
+        from .solver_launcher import census_report
+        c = t.census(rem_bins=args.rem_bins)
+        wit = [(e["count"], e["max_remoteness"], None if e["key"] is None else spec.pos_of(e["key"]))
+               for e in c["extremes"]]
+        print(census_report(c["by_remoteness"], c["by_level"], wit)[0])
+        return 0
+    todo = [ast.literal_eval(p) for p in args.positions] or [mod.initial_position()]
+    keys, known = [], []
+    for pos in todo:
+        try:
+            keys.append(spec.key_of(pos))
+            known.append(True)
+        except _lib.GmError:  # no key: outside the game's state space
+            keys.append(_lib.GM_EMPTY_KEY)
+            known.append(False)
+    keys = np.array(keys, np.uint64)
+    words = t.query(keys)
+    children, cwords, nchild, best = t.moves(keys) if args.moves else (None, None, None, None)
+    rc = 0
+    for i, pos in enumerate(todo):
+        w = int(words[i])
+        if not known[i] or w == NO_WORD:
+            print("%s: not reachable" % (pos,))
+            rc = 1
+            continue
+        print("%s: %s in %d moves" % (pos, NAMES[w & 3], w >> 2))
+        if args.moves and nchild[i]:
+            for j, mv in enumerate(mod.gen_moves(pos)):
+                cw = int(cwords[i, j])
+                what = "not reachable" if cw == NO_WORD else "%s in %d moves" % (NAMES[cw & 3], cw >> 2)
+                print("  %s -> %s: %s%s" % (mv, mod.do_move(pos, mv), what, " *" if j == int(best[i]) else ""))
+                if cw == NO_WORD:
+                    rc = 1
+    return rc
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="gamesmanmpi_amd.db")
     ap.add_argument("statsdir")
@@ -676,8 +762,17 @@ def main(argv=None):
                          "stats/0/solution.gmtb (indexed games: four_to_one, sum_four_to_one, "
                          "toot_and_otto_bitstring) or, for the other descriptor games, to the keyed "
                          "tablebase stats/0/solution.gmtk, and exit")
+    ap.add_argument("--gpu", action="store_true",
+                    help="open the directory's tablebase (solution.gmtb / solution.gmtk) on the GPU "
+                         "(Solver.open_tablebase) and answer there: queries and --moves from the device, "
+                         "--census with the by-level table, --audit")
+    ap.add_argument("--audit", action="store_true",
+                    help="--gpu: re-derive every stored word from its children's stored words; prints the "
+                         "counts and up to 64 mismatching positions, exit status 1 on a mismatch")
     ap.add_argument("positions", nargs="*")
     args = ap.parse_intermixed_args(argv)
+    if args.audit and not args.gpu:
+        ap.error("--audit reads the tablebase on the device: add --gpu")
     from . import _lib
     from .solver_launcher import ensure_src_utils, load_game
     ensure_src_utils()
@@ -695,6 +790,8 @@ def main(argv=None):
     if db.by == "key":
         from .games import spec_for_module
         spec = spec_for_module(mod, os.path.splitext(os.path.basename(args.game))[0])
+    if args.gpu:
+        return gpu_main(args, db, mod, spec)
     if args.census:
         c = db_census(db, spec, args.rem_bins)
         print(format_census(c["by_remoteness"], c["by_level"]))

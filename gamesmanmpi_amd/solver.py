@@ -589,6 +589,21 @@ class Solver:
         return {"path": path, "bytes": total, "positions": npos, "word_bytes": wb, "key_bytes": kb,
                 "bucket_bits": b}
 
+    @staticmethod
+    def open_tablebase(spec, path, device=None):
+        """A saved tablebase (solution.gmtb / solution.gmtk) opened on the GPU
+        (gm_solver_open_table; gamesmanmpi_amd.table.OpenTable): the file's
+        bytes streamed through one pinned chunk into one device buffer and
+        read in place.  The returned object answers query / positions /
+        checksum / moves / best_line / audit / census / export_tablebase /
+        export_keyed_tablebase as a Solver that has just solved does, and
+        raises GmError(GM_EINVAL) for solve(), solve_steps() and checkpoints.
+        GmError(GM_EINVAL) for a file whose header is wrong (what db.Tablebase
+        / db.KeyedTablebase refuse), GmError(GM_ECORRUPT) for one whose bitmap
+        and counts, or directory and keys, disagree."""
+        from .table import OpenTable
+        return OpenTable(spec, path, device=device)
+
     def dump(self):
         """(keys u64, value u8, remoteness u32) for every reachable
         position."""

@@ -89,6 +89,11 @@ typedef struct gm_slot {
  * the levels buffer is unused.  GM_F_FORCE_HASHED / GM_F_HASH_TABLE keep
  * the keyed layouts. */
 #define GM_MODE_RANKED 4u
+/* FILE (gm_solver_open_table only; gm_plan never chooses it): the bytes of a
+ * saved tablebase, solution.gmtb or solution.gmtk, in device memory -- read
+ * in place by the readers, never solved
+ * (gamesmanmpi_amd/csrc/gm_table_file.h). */
+#define GM_MODE_FILE 5u
 
 /* Sizes the caller must allocate for a solve (see gm_plan). */
 typedef struct gm_plan_t {
@@ -479,6 +484,52 @@ int gm_solver_export_keyed(gm_solver *s, uint32_t how, uint32_t bucket_bits,
                            uint32_t word_bytes, void *stage_dev,
                            uint64_t *dir_dev, void *keys_dev, void *words_dev,
                            uint64_t cap, uint64_t out[4]);
+/* ---- a saved tablebase opened on the device --------
+ * Replaces reading a saved solution back one key at a time
+ * (src/cache_dict.py:62-79): the file's bytes in device memory serve every
+ * reader of a solved table, nothing is re-solved.
+ *
+ * Host only, no GPU needed: the 64 header bytes of a solution.gmtb /
+ * solution.gmtk against the file's byte count -- the refusals of
+ * db.Tablebase / db.KeyedTablebase (gamesmanmpi_amd/db.py): magic, version,
+ * word / key bytes and bucket bits, section offsets against the sizes, the
+ * byte count, and for a gmtb an index space other than gm_tb_info's (games
+ * without an index: gm_tb_info's error).  GM_EINVAL with the reason in
+ * gm_last_error.  out[0] = format (1 gmtb, 2 gmtk), out[1] = positions,
+ * out[2] = word bytes, out[3] = key bytes (gmtk), out[4] = bucket bits
+ * (gmtk), out[5] = index space (gmtb), out[6..8] = offsets of the bitmap /
+ * directory, the counts / keys and the words, out[9] = scratch bytes
+ * gm_solver_open_table needs (gm_plan's scratch_bytes rounded up to 256, plus
+ * out[10]), out[10] = bytes of the index tables it uploads (toot gmtb: first
+ * slots per height vector, level tables, packed heights), out[11] = 0. */
+int gm_table_check(int game, const void *header, uint64_t header_bytes,
+                   uint64_t file_bytes, uint64_t out[12]);
+/* A solver over the file image at image_dev (`bytes` = the whole file,
+ * 256-byte aligned, caller-owned like every buffer): mode GM_MODE_FILE, one
+ * GPU, holding a finished solve.  The image is read in place -- keys are not
+ * expanded, words not widened -- and must stay valid and unchanged while the
+ * solver lives; scratch_dev (256-byte aligned, gm_table_check's out[9] bytes)
+ * too.  stream: hipStream_t to run on (NULL: the library's own).
+ * The header is checked as gm_table_check does; then one kernel checks every
+ * range a reader will follow -- gmtb: the counts start at 0, never decrease,
+ * each step is the popcount of its block's eight bitmap words, the last count
+ * is the position count, and every reached index is a position of the game;
+ * gmtk: the directory starts at 0, never decreases and ends at the position
+ * count, and every bucket's keys ascend strictly.  A violation is
+ * GM_ECORRUPT, gm_last_error names the first offending block / bucket, and
+ * no solver is returned.  Stored WORDS are not checked here: gm_solver_audit
+ * on the returned solver re-derives every one of them.
+ * Served: gm_solver_query, _positions, _checksum, _moves, _line, _audit,
+ * _census, _export, _export_keyed (the `how` argument of the last three is
+ * ignored: an image has no storage-order kernels, every call takes the
+ * enumerator and the query path), gm_solver_destroy.  On a symmetric table
+ * keys are mapped to their orbit representatives with the game's own flags,
+ * as the layout that wrote the file does.  Refused with GM_EINVAL:
+ * gm_solver_solve, _solve_async, gm_solve_group, gm_solver_set_steps,
+ * _set_flags, _set_transport and the gm_ks_* calls. */
+int gm_solver_open_table(int game, const void *image_dev, uint64_t bytes,
+                         void *scratch_dev, uint64_t scratch_bytes,
+                         void *stream, gm_solver **out);
 /* change GM_F_* flags of an existing solver (e.g. kernel timing) */
 int gm_solver_set_flags(gm_solver *s, uint32_t flags);
 /* Level-granular stop / resume (checkpoints; SURVEY.md §8f rank 2 -- the
