@@ -132,7 +132,7 @@ EXPORTS = (
     "gm_shard_info", "gm_solver_set_transport", "gm_shard_halo_sigs", "gm_plane_halo_plan", "gm_rk_shard_stats",
     "gm_ks_begin", "gm_ks_level_size", "gm_ks_expand", "gm_ks_insert",
     "gm_ks_finalize", "gm_ks_counts", "gm_ks_children", "gm_ks_reduce",
-    "gm_ks_end", "gm_graph_solve",
+    "gm_ks_end", "gm_graph_solve", "gm_graph_solve_loopy",
     "gm_tb_info", "gm_tb_index", "gm_ranked_slots", "gm_solver_export",
     "gm_mix64", "gm_solver_export_keyed", "gm_table_check", "gm_solver_open_table",
     "gm_last_error", "gm_version",
@@ -242,6 +242,9 @@ def load():
         "gm_graph_solve": [c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64,
                            c.c_uint64, c.c_void_p, c.c_void_p, c.c_void_p,
                            P(gm_result)],
+        "gm_graph_solve_loopy": [c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64,
+                                 c.c_uint64, c.c_void_p, c.c_void_p, c.c_void_p,
+                                 P(gm_result), P(c.c_uint64)],
     }
     for name, args in sig.items():
         f = getattr(L, name)

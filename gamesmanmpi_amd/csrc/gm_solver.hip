@@ -2498,3 +2498,5 @@ int gm_graph_solve(const uint8_t* prim_dev, const uint64_t* offsets_dev, const u
   out->root_remoteness = root_word >> 2;
   return 0;
 }
+
+#include "gm_graph_loopy.h"

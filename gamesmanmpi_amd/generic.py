@@ -7,7 +7,11 @@ Here the host does exactly that enumeration -- the module's own functions,
 breadth first from initial_position() -- and builds a CSR graph of the
 reachable positions; the retrograde pass runs on the GPU
 (gm_graph_solve: rounds of "resolve every position whose children are all
-resolved", the same reduction as the descriptor pipeline).
+resolved", the same reduction as the descriptor pipeline).  A module whose
+positions repeat enumerates to a finite graph with back edges (positions are
+identified by str(pos)); gm_graph_solve refuses it, loopy=True solves it
+with gm_graph_solve_loopy (attractor WIN / LOSS, TIE,
+and DRAW for what is left).
 
 Positions are identified by str(pos), the identity the reference itself
 hashes (GameState.get_hash, src/game_state.py:22-30); two positions with the
@@ -88,10 +92,18 @@ def enumerate_game(module, limit=50_000_000, keep_positions=False):
                      objs if keep_positions else None)
 
 
-class GenericSolver:
-    """Solve an enumerated GameGraph on one GPU (no descriptor needed)."""
+def loopy_scratch_bytes(n):
+    """GM_GRAPH_LOOPY_SCRATCH_BYTES(n) of include/gamesman.h."""
+    return 4096 + 8 * int(n)
 
-    def __init__(self, graph, device=None):
+
+class GenericSolver:
+    """Solve an enumerated GameGraph on one GPU (no descriptor needed).
+    loopy=True: the graph may have cycles (gm_graph_solve_loopy); the result's
+    extra then holds "loopy": True and the positions by rule, "founded",
+    "attractor", "tie" and "draw"."""
+
+    def __init__(self, graph, device=None, loopy=False):
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("gamesmanmpi_amd needs a ROCm GPU (gfx950); "
@@ -99,6 +111,7 @@ class GenericSolver:
         self.torch = torch
         self.graph = graph
         self.device = torch.device(device if device is not None else "cuda")
+        self.loopy = bool(loopy)
         self.words = None
 
     def solve(self):
@@ -111,13 +124,21 @@ class GenericSolver:
             ch = g.children if len(g.children) else np.zeros(1, np.uint32)
             children = torch.from_numpy(ch.view(np.int32)).to(dev)
             words = torch.empty(g.n, dtype=torch.int32, device=dev)
-            scratch = torch.zeros(4096, dtype=torch.uint8, device=dev)
+            # loopy: GM_GRAPH_LOOPY_SCRATCH_BYTES(n), two lists of open positions behind the 4 KB
+            scratch = torch.zeros(loopy_scratch_bytes(g.n) if self.loopy else 4096,
+                                  dtype=torch.uint8, device=dev)
             stream = torch.cuda.current_stream(dev)
             r = _lib.gm_result()
-            _lib.check(_lib.load().gm_graph_solve(
-                prim.data_ptr(), offsets.data_ptr(), children.data_ptr(),
-                g.n, 0, words.data_ptr(), scratch.data_ptr(),
-                stream.cuda_stream, ctypes.byref(r)))
+            args = (prim.data_ptr(), offsets.data_ptr(), children.data_ptr(),
+                    g.n, 0, words.data_ptr(), scratch.data_ptr(),
+                    stream.cuda_stream, ctypes.byref(r))
+            extra = {}
+            if self.loopy:
+                counts = (ctypes.c_uint64 * 4)()
+                _lib.check(_lib.load().gm_graph_solve_loopy(*args, counts))
+                extra = dict(zip(("founded", "attractor", "tie", "draw"), (int(c) for c in counts)), loopy=True)
+            else:
+                _lib.check(_lib.load().gm_graph_solve(*args))
         self.words = words.cpu().numpy().view(np.uint32)
         return SolveResult(
             root_value=r.root_value, root_remoteness=r.root_remoteness,
@@ -125,9 +146,9 @@ class GenericSolver:
             levels=r.levels, max_level_width=0, ms_total=r.ms_total,
             ms_forward=0.0, ms_backward=r.ms_total,
             n_resolve_launches=r.n_resolve_launches,
-            extra={"layout": "graph", "rounds": r.levels,
-                   "host_enumeration_s": getattr(g, "enum_s", None),
-                   "wall_s": time.perf_counter() - t0})
+            extra=dict(extra, layout="graph", rounds=r.levels,
+                       host_enumeration_s=getattr(g, "enum_s", None),
+                       wall_s=time.perf_counter() - t0))
 
     def dump(self):
         """(names, value u8, remoteness u32) for every reachable position."""
@@ -135,10 +156,10 @@ class GenericSolver:
         return self.graph.names, (w & 3).astype(np.uint8), (w >> 2).astype(np.uint32)
 
 
-def solve_module(module, device=None, limit=50_000_000):
+def solve_module(module, device=None, limit=50_000_000, loopy=False):
     """Enumerate `module` on the host and solve it on the GPU."""
     t0 = time.perf_counter()
     g = enumerate_game(module, limit=limit)
     g.enum_s = time.perf_counter() - t0
-    s = GenericSolver(g, device=device)
+    s = GenericSolver(g, device=device, loopy=loopy)
     return s.solve(), s

@@ -128,7 +128,20 @@ def build_parser():
                         "GPU and read by mmap (gamesmanmpi_amd.db) instead of solution.npz -- the "
                         "indexed solution.gmtb for four_to_one, sum_four_to_one and "
                         "toot_and_otto_bitstring, the keyed solution.gmtk for the other games")
+    p.add_argument("--loopy", action="store_true",
+                   help="graph solves (no descriptor, or --layout graph): the game's positions may "
+                        "repeat; positions from which play can go on forever get attractor WIN / "
+                        "LOSS values, TIE, or DRAW in 0 (DESIGN.md section 7k) instead of the "
+                        "`never resolve` error")
     return p
+
+
+def check_loopy_args(args, descriptor=True):
+    """--loopy is a mode of the host-enumerated graph path only."""
+    if args.loopy and descriptor and args.layout != "graph":
+        raise SystemExit("--loopy: only the host-enumerated graph path solves games whose positions repeat "
+                         "(a file without a device descriptor, or --layout graph); layout %r is a "
+                         "descriptor layout" % args.layout)
 
 
 def check_tablebase_args(args, world, spec=None, descriptor=True):
@@ -323,7 +336,8 @@ def solve_generic(args, game, rank, world, local):
     from gamesmanmpi_amd.generic import solve_module
     if rank == 0:
         torch.cuda.set_device(local)
-        result, solver = solve_module(game, device="cuda:%d" % local)
+        result, solver = solve_module(game, device="cuda:%d" % local, loopy=args.loopy)
+        by_rule = {k: result.extra[k] for k in ("founded", "attractor", "tie", "draw")} if args.loopy else {}
         print(result.root_line, flush=True)  # src/process.py:47-52
         census = host_census(*solver.dump()) if args.census else None
         if args.json:
@@ -334,6 +348,8 @@ def solve_generic(args, game, rank, world, local):
                    "ms_total": result.ms_total,
                    "host_enumeration_s": result.extra["host_enumeration_s"],
                    "layout": "graph", "ranks": 1}
+            if args.loopy:
+                row.update(by_rule, loopy=True)
             if census:
                 row["census"] = census[1]
             print(json.dumps(row), flush=True)
@@ -346,12 +362,14 @@ def solve_generic(args, game, rank, world, local):
             names, val, rem = solver.dump()
             np.savez_compressed(os.path.join(d, "solution.npz"),
                                 names=np.array(names), value=val, remoteness=rem)
+            meta = {"game": os.path.basename(args.game_file),
+                    "root": result.root_line, "positions": len(names),
+                    "layout": "graph", "key": "str(position)",
+                    "value_codes": {"WIN": 0, "LOSS": 1, "TIE": 2, "DRAW": 3}}
+            if args.loopy:
+                meta.update(by_rule, loopy=True)
             with open(os.path.join(d, "meta.json"), "w") as f:
-                json.dump({"game": os.path.basename(args.game_file),
-                           "root": result.root_line, "positions": len(names),
-                           "layout": "graph", "key": "str(position)",
-                           "value_codes": {"WIN": 0, "LOSS": 1, "TIE": 2, "DRAW": 3}},
-                          f, indent=1)
+                json.dump(meta, f, indent=1)
     return 0
 
 
@@ -386,6 +404,7 @@ def main(argv=None):
             raise
         check_analysis_args(args, world, descriptor=False)
         check_tablebase_args(args, world, descriptor=False)
+        check_loopy_args(args, descriptor=False)
         logging.debug("%s: solving through the host-enumerated graph", e)
         return solve_generic(args, game, rank, world, local)
     if args.layout == "graph":
@@ -393,6 +412,7 @@ def main(argv=None):
             raise SystemExit("--board-symmetry: the host-enumerated graph path (--layout graph) has no board group")
         return solve_generic(args, game, rank, world, local)
     check_tablebase_args(args, world, spec)
+    check_loopy_args(args)
     if args.symmetries:
         if not hasattr(game, "symmetry_functions"):
             raise SystemExit("%s defines no symmetry_functions()" % args.game_file)

@@ -668,6 +668,34 @@ int gm_graph_solve(const uint8_t *prim_dev, const uint64_t *offsets_dev,
                    uint32_t *words_dev, void *scratch_dev, void *stream,
                    gm_result *out);
 
+/* The same graph, cycles allowed (game files whose positions repeat; DESIGN.md
+ * §7k).  Arguments, refusals and result counters as gm_graph_solve, and an
+ * UNDECIDED position without moves is the same error; n <= 2^32 - 1.  Call a
+ * position FOUNDED when gm_graph_solve's rule reaches it (no cycle is
+ * reachable from it), UNFOUNDED otherwise.  Every position gets one word:
+ *   A  a founded position: the word gm_graph_solve gives it (WIN: 1 + the
+ *      least remoteness of its LOSS children; every other value: 1 + the
+ *      largest remoteness of ALL its children).  On a graph without cycles
+ *      the words are those of gm_graph_solve, bit for bit.
+ *   B  an unfounded position is WIN if some child is LOSS, in 1 + the least
+ *      remoteness of its LOSS children, and LOSS if every child is WIN, in
+ *      1 + the largest child remoteness (least fixpoint; founded and
+ *      unfounded children count alike).
+ *   C  of what B leaves: TIE if some child is TIE (least fixpoint), in 1 +
+ *      the LEAST remoteness of its TIE children -- the shortest way to the
+ *      tie, since "the largest over all children" of rule A has no meaning
+ *      when a child sits on a cycle.
+ *   D  everything else: GM_DRAW in 0 (word 3).
+ * counts (host memory, may be NULL): positions founded and resolved by B, C
+ * and D; they add up to n.  result.levels = n_resolve_launches = the round
+ * launches of all phases, at most 2 n + 8 (GM_ECORRUPT beyond).
+ * scratch_dev: GM_GRAPH_LOOPY_SCRATCH_BYTES(n) bytes. */
+#define GM_GRAPH_LOOPY_SCRATCH_BYTES(n) (4096 + 8 * (uint64_t)(n))
+int gm_graph_solve_loopy(const uint8_t *prim_dev, const uint64_t *offsets_dev,
+                         const uint32_t *children_dev, uint64_t n, uint64_t root,
+                         uint32_t *words_dev, void *scratch_dev, void *stream,
+                         gm_result *out, uint64_t counts[4]);
+
 /* One-shot pair: gm_solve creates a solver on the caller's
  * buffers and solves from the game's root; the solver is kept per game id
  * (the buffers must stay valid) until the next gm_solve of that game or
